@@ -1,17 +1,26 @@
 """Throughput benchmark: InterNet (HRNet) training steps on synthetic 256x512 len-3 clips.
 
-    python bench.py [--gpus N --steps K --warmup W]            (N>1: launched by torchrun)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                                                               (N>1: launched by torchrun)
 
 Workload (BASELINE.json configs[1]): InterNet int_5_len_3, 256x512, bf16 compute, per-GPU
 batch 8 synthetic Cityscapes-shaped triplets resident in HBM; one step = the reference's
 InterTrainer step body (HRNet fwd, RGBLoss (L1+GDL+SSIM+VGG19) + 30*CE, backward, RCCL
 gradient all-reduce, Adamax).  Metric: synthesized frames/s (one per clip), whole job.
 
-After the timed region, 2 extra profiling steps time every plan op with HIP events on the
-launch stream; the dominant kernel family (the conv forward + data-gradient kernels) is
-reported against the bf16 MFMA peak as `roofline`.  Rank 0 at N=1 also times the
-CPU oracle (the reference algorithm restated in PyTorch-CPU fp32) on a bounded sample as
-`cpu_baseline`.
+A plain run sets up, warms up, times the K steps and prints the one JSON result line
+(`value`, `ms_per_step`, ...).  --dump-outputs DIR also writes what the last timed step
+returned to its caller (the step's loss dict) as DIR/<name>.npy (float32); the inputs, the
+initial weights and therefore these values are the same from run to run with the same
+arguments.
+
+--full adds everything else to the line: after the timed region, 2 extra profiling steps
+time every plan op with HIP events on the launch stream; the dominant kernel family (the
+conv forward + data-gradient kernels) is reported against the bf16 MFMA peak as `roofline`,
+the warp and clip-pipeline kernels against the HBM roofline, and rank 0 at N=1 also times
+the CPU oracle (the reference algorithm restated in PyTorch-CPU fp32) on a bounded sample
+as `cpu_baseline`.  (A captured-step workload, --graph 1, times the eager step and then the
+replay in either mode: the capture follows those eager steps.)
 """
 import argparse
 import json
@@ -50,9 +59,16 @@ def parse():
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=2)
-    ap.add_argument("--ops-out", default=None, help="write the per-op profile table (profiling steps) here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (its loss dict) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-op profiling steps (roofline, step breakdown), "
+                         "the warp / clip-pipeline rooflines and the CPU baseline; off: the line carries the "
+                         "throughput figures only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--profile-steps", type=int, default=2, help="with --full: profiling steps after the timed ones")
+    ap.add_argument("--ops-out", default=None,
+                    help="with --full: write the per-op profile table (profiling steps) here")
     ap.add_argument("--workload", default="c2", choices=["c2", "c5"],
                     help="c2: BASELINE configs[1] (InterNet 256x512 bf16, batch 8; the default line); c5: "
                          "BASELINE configs[4] per GPU (two-stage extrapolation ExtraStage3Net 1024x2048 bf16, batch "
@@ -61,7 +77,12 @@ def parse():
                     help="1: time the hipGraph-captured step (runners/graph.py), 0: the eager step; default 0 for "
                          "c2 (same box, r04v: eager 34.9 ms with the executor's weight lane vs 35.4 ms captured -- "
                          "a capture keeps every op on one stream), 1 for c5 (the config names a captured step)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.ops_out and not a.full:
+        ap.error("--ops-out needs --full (the table comes from the profiling steps)")
+    return a
 
 
 def make_batch(n, H, W, device, first):
@@ -293,6 +314,15 @@ def refuse_timing_switches(env=os.environ):
         sys.exit(2)
 
 
+def dump_outputs(path, ld):
+    """--dump-outputs: the loss dict a caller of the timed step received from its last step,
+    one float32 array of one element per entry, as path/<name>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in ld.items():
+        np.save(os.path.join(path, f"{k}.npy"), v.detach().float().cpu().numpy().reshape(-1).astype(np.float32))
+
+
 def main():
     refuse_timing_switches()
     a = parse()
@@ -319,7 +349,6 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
 
-    from deep_video_interpolation_extrapolation_amd import engine
     from deep_video_interpolation_extrapolation_amd.options import default_args
     from deep_video_interpolation_extrapolation_amd.runners.InterTrainer import InterTrainer
 
@@ -370,11 +399,24 @@ def main():
         gstep = GraphedStep(trainer, data, warmup=1)  # the batch now lives in the graph's static inputs
         dt, ld = timed(lambda _d: gstep.step())
         loss_all = float(ld["loss_all"])
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, ld)  # before close(): the graph owns these tensors
         gstep.close()  # eager profiling steps below: in-backward bucket overlap back on (W > 1)
     else:
         loss_all = float(ld["loss_all"])
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, ld)
+    roof, agg = profile_report(a, trainer, data, dev, rank) if a.full else (None, {})
+    report(a, dt, eager_dt, loss_all, roof, agg, dev, rank, world)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
 
-    # ---- profiling steps: per-op HIP events on the launch stream ----
+
+def profile_report(a, trainer, data, dev, rank):
+    """--full: the profiling steps (per-op HIP events on the launch stream) -> (roofline of
+    the conv fwd + dgrad family, per-class totals); writes the --ops-out table."""
+    from deep_video_interpolation_extrapolation_amd import engine
     prof = []
     if a.profile_steps > 0:
         engine.PROFILE = prof
@@ -448,7 +490,11 @@ def main():
                 rt = max(o["flops"] / (peak * 1e12), o["bytes"] / (PEAK_HBM_GBS * 1e9))
                 f.write(f"{cls:12s} {name[:42]:42s} {o['n']:3d} {o['ms'] / a.profile_steps:8.3f} "
                         f"{o['flops'] / t / 1e12:8.1f} {o['bytes'] / t / 1e9:8.1f} {100 * rt / t:6.1f}\n")
+    return roof, agg
 
+
+def report(a, dt, eager_dt, loss_all, roof, agg, dev, rank, world):
+    """The one JSON line (rank 0); with --full also the roofline / baseline legs it carries."""
     if rank == 0:
         frames = a.batch * world * a.steps
         c5 = a.workload == "c5"
@@ -472,10 +518,13 @@ def main():
                        "per_gpu_batch": a.batch, "global_batch": a.batch * world, "parallelism": f"dp{world}",
                        "step": "hipGraph-captured" if a.graph else "eager, executor side-stream lanes"},
             "eager_ms_per_step": round(eager_dt * 1e3 / a.steps, 3),
-            "roofline": roof,
             "loss_all": loss_all,
-            "step_breakdown_ms": {k: round(v["ms"] / max(1, a.profile_steps), 3) for k, v in sorted(agg.items())},
         }
+        if not a.full:
+            print(json.dumps(out), flush=True)
+            return
+        out["roofline"] = roof
+        out["step_breakdown_ms"] = {k: round(v["ms"] / max(1, a.profile_steps), 3) for k, v in sorted(agg.items())}
         at = [agg[c] for c in ("attn", "attn_bwd") if c in agg]
         if at:  # local-window attention of the stage-3 net (HBM-bound gathers / reductions)
             ms, by = sum(r["ms"] for r in at), sum(r["bytes"] for r in at)
@@ -491,9 +540,6 @@ def main():
         else:
             out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -41,6 +41,50 @@ def test_gpus_n_spawns_child_torchrun(monkeypatch):
     assert env["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch, capsys):
+    """--full is off by default; the options that only mean something with the profiling
+    steps are refused without it instead of being silently ignored; --steps >= 1."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 4, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--ops-out", "ops.txt", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.ops_out == "ops.txt" and a.dump_outputs == "d"
+    for argv in (["--ops-out", "ops.txt"], ["--steps", "0"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.parse()
+        assert e.value.code == 2
+    capsys.readouterr()
+
+
+def test_dump_outputs_writes_one_float32_array_per_loss(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    ld = {"loss_all": torch.tensor(1.5, dtype=torch.float64), "coarse_l1_loss": torch.tensor([0.25]).bfloat16()}
+    out = tmp_path / "sub" / "dump"
+    bench.dump_outputs(str(out), ld)
+    assert sorted(p.name for p in out.iterdir()) == ["coarse_l1_loss.npy", "loss_all.npy"]
+    for k, v in (("loss_all", 1.5), ("coarse_l1_loss", 0.25)):
+        x = np.load(out / f"{k}.npy")
+        assert x.dtype == np.float32 and x.shape == (1,) and float(x[0]) == v
+
+
+def test_report_line_plain_vs_full(capsys):
+    """A plain run's line carries the throughput figures and none of the --full legs."""
+    import json
+    import bench
+    a = type("A", (), dict(batch=8, steps=4, warmup=1, workload="c2", precision="bf16", height=256, width=512,
+                           graph=0, full=False))()
+    bench.report(a, 0.2, 0.2, 3.0, None, {}, None, 0, 1)
+    d = json.loads(capsys.readouterr().out)
+    assert d["ms_per_step"] == 50.0 and d["value"] == 160.0 and d["steps"] == 4 and d["unit"] == "frames/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16" and d["metric"].startswith("train frames/s")
+    assert not {"roofline", "step_breakdown_ms", "cpu_baseline", "warp", "clip_prep"} & set(d)
+
+
 def test_bench_refuses_timing_switches():
     """A DVIE_*_DBG variable (timing-only kernel ablations, wrong results) makes bench.py exit
     non-zero before anything runs."""

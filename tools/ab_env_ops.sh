@@ -8,7 +8,7 @@ out=gpurun_out/$tag; mkdir -p $out
 i=0
 for e in "$@"; do
   [ "$e" = "-" ] && e=""
-  env $e timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --ops-out $out/ops_$i.txt > $out/b_$i.json 2> $out/b_$i.err || { echo "run $i ($e) failed"; tail -20 $out/b_$i.err; exit 1; }
+  env $e timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --ops-out $out/ops_$i.txt > $out/b_$i.json 2> $out/b_$i.err || { echo "run $i ($e) failed"; tail -20 $out/b_$i.err; exit 1; }
   echo "$i [$e] $(python3 -c "import json;d=json.load(open('$out/b_$i.json'));print(d['value'], d['ms_per_step'], d['step_breakdown_ms'])")"
   i=$((i+1))
 done

@@ -12,6 +12,7 @@ for r in 1 2; do
   for v in a b; do
     if [ $v = a ]; then cp "$la" $pkg; else cp "$lb" $pkg; fi
     timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --ops-out gpurun_out/$tag/ops_${v}_$r.txt \
+      --full \
       > gpurun_out/$tag/b_${v}_$r.json 2> gpurun_out/$tag/b_${v}_$r.err || { tail -20 gpurun_out/$tag/b_${v}_$r.err; exit 1; }
     echo "lib $v run $r $(grep -o '"value": [0-9.]*' gpurun_out/$tag/b_${v}_$r.json)"
   done

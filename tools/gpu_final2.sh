@@ -7,7 +7,7 @@ set -o pipefail
 tag=${1:-final2}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag; mkdir -p $out
-timeout -k 10 600 python -u bench.py --workload c5 --ops-out $out/ops_c5.txt > $out/bench_c5.json 2> $out/bench_c5.err \
+timeout -k 10 600 python -u bench.py --full --workload c5 --ops-out $out/ops_c5.txt > $out/bench_c5.json 2> $out/bench_c5.err \
   || { echo "c5 bench failed"; tail -20 $out/bench_c5.err; exit 1; }
 cat $out/bench_c5.json
 bash tools/pmc_bench.sh $tag/pmc > /dev/null || exit 1

@@ -1,4 +1,4 @@
-"""Summarise a bench.py --ops-out table: ms per step by class and the ops that lose the most
+"""Summarise a bench.py --full --ops-out table: ms per step by class and the ops that lose the most
 time against their roofline (ms * (1 - roof%)).  usage: python tools/ops_lost.py ops.txt [N]"""
 import sys
 
