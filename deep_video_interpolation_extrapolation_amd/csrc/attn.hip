@@ -17,7 +17,6 @@
 
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace dvie {
 
@@ -660,15 +659,7 @@ __global__ __launch_bounds__(256) void attn_gather_mfma_kernel(const dvie_attn_d
     if (r + 1 < p.wh) continue;
     // epilogue: permlane32 pairing -> 8 consecutive channels of one pixel per lane
     float v[2][8];
-#pragma unroll
-    for (int P = 0; P < 2; ++P)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[8 * P + e]), __float_as_uint(acc[8 * P + 4 + e]),
-                                                         false, false);
-        v[P][e] = __uint_as_float(sw[0]);
-        v[P][4 + e] = __uint_as_float(sw[1]);
-      }
+    acc_rows8(acc, v);
     const int q = 32 * pb + r32;
     if (q < npx) {
 #pragma unroll

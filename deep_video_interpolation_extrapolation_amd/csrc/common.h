@@ -10,6 +10,9 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // one 32x32 MFMA accumulator
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 typedef uint16_t bf16_t;  // raw bf16 storage
 
@@ -60,6 +63,12 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
   if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x007fffffu)) return (bf16_t)((u >> 16) | 0x40);
   u += 0x7fffu + ((u >> 16) & 1u);
   return (bf16_t)(u >> 16);
+}
+
+// two floats -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32; = f2bf for every
+// non-NaN input, a quiet NaN for NaN)
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{a, b}), bf16x2));
 }
 
 // 4-element vector access (fp32: 16 B, bf16: 8 B)
@@ -144,6 +153,22 @@ __device__ __forceinline__ float act_dz(float z, int act, float alpha) {
     case DVIE_ACT_TANH: return 1.f - z * z;
     default: return 1.f;
   }
+}
+
+// Accumulator transposition (v_mfma_f32_32x32x16 layout): permlane32_swap pairs the half-waves
+// so that each lane owns 8 consecutive channels of one pixel -- lane half h ends with channels
+// 16P + 8h .. +7 of pair P in v[P].  (The halo-family kernels keep this loop written out: through
+// the helper their register allocation shifts, conv_halo.hip by up to 10 VGPRs.)
+__device__ __forceinline__ void acc_rows8(const f32x16& acc, float (*v)[8]) {
+#pragma unroll
+  for (int P = 0; P < 2; ++P)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[8 * P + e]), __float_as_uint(acc[8 * P + 4 + e]),
+                                                       false, false);
+      v[P][e] = __uint_as_float(sw[0]);
+      v[P][4 + e] = __uint_as_float(sw[1]);
+    }
 }
 
 __host__ __device__ __forceinline__ int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }

@@ -17,53 +17,13 @@
 // bottleneck conv1/conv3, downsample, fuse and final layers).
 #include <stdlib.h>
 
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "conv_epilogue.h"
 
 namespace dvie {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_1x1;
 
 #define DVIE_VMCNT1(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | (((N) >> 4) << 14) | (7 << 4) | (15 << 8))
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{a, b}), bf16x2));
-}
-
-__device__ __forceinline__ void act1(float* v, int act, float alpha) {
-  if (act == DVIE_ACT_LRELU) {
-    for (int k = 0; k < 8; ++k) v[k] = v[k] > 0.f ? v[k] : v[k] * alpha;
-  } else if (act == DVIE_ACT_RELU) {
-    for (int k = 0; k < 8; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
-  } else if (act == DVIE_ACT_ELU) {
-    for (int k = 0; k < 8; ++k) v[k] = elu_bf(v[k]);  // (bf16-input kernels: common.h)
-  } else if (act == DVIE_ACT_TANH) {
-    for (int k = 0; k < 8; ++k) v[k] = tanh_bf(v[k]);
-  }
-}
-
-__device__ __forceinline__ void dact1(float* v, const float* z, int dact, float alpha) {
-  if (dact == DVIE_ACT_LRELU) {
-    for (int k = 0; k < 8; ++k) v[k] *= z[k] > 0.f ? 1.f : alpha;
-  } else if (dact == DVIE_ACT_RELU) {
-    for (int k = 0; k < 8; ++k) v[k] = z[k] > 0.f ? v[k] : 0.f;
-  } else if (dact == DVIE_ACT_ELU) {
-    for (int k = 0; k < 8; ++k) v[k] *= z[k] > 0.f ? 1.f : z[k] + 1.f;
-  } else if (dact == DVIE_ACT_TANH) {
-    for (int k = 0; k < 8; ++k) v[k] *= 1.f - z[k] * z[k];
-  }
-}
-
-__device__ __forceinline__ void unpack8(const i32x4 t, float* v) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[2 * e] = __uint_as_float(((uint32_t)t[e]) << 16);
-    v[2 * e + 1] = __uint_as_float(((uint32_t)t[e]) & 0xffff0000u);
-  }
-}
 
 // 8 x 8 transpose of 16-B chunks inside each 8-lane group: (lane b, chunk k) <-> (lane k,
 // chunk b); at distance d the lane with bit d set trades its chunk k for the partner's chunk
@@ -334,16 +294,7 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_kernel(const dvie_conv
   const int pix = CE ? min(pix0, npix - 1) : pix0;  // (CE: every lane takes part in the shuffles)
   float v[TMC][2][8];
 #pragma unroll
-  for (int j = 0; j < TMC; ++j)
-#pragma unroll
-    for (int P = 0; P < 2; ++P)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[i][j][8 * P + e]),
-                                                         __float_as_uint(acc[i][j][8 * P + 4 + e]), false, false);
-        v[j][P][e] = __uint_as_float(sw[0]);
-        v[j][P][4 + e] = __uint_as_float(sw[1]);
-      }
+  for (int j = 0; j < TMC; ++j) acc_rows8(acc[i][j], v[j]);
   if (!CE && pix >= npix) continue;
   long long yp = pix;
   if (p.osy != 1 || p.osx != 1 || p.ory != 0 || p.orx != 0 || p.yh != p.oh || p.yw != p.ow) {
@@ -359,71 +310,31 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_kernel(const dvie_conv
       const int co = c0 + wc * 32 * TMC + 32 * j + 16 * P + 8 * hh;
       if (!CE && co >= p.cout) continue;
       float* w = v[j][P];
-      if (p.bias) {
-        const f32x4 b0 = *(const f32x4*)(p.bias + co), b1 = *(const f32x4*)(p.bias + co + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          w[e] += b0[e];
-          w[4 + e] += b1[e];
-        }
-      }
       if constexpr (OUTF32) {
-        float* dst = (float*)p.y + yp * p.y_ld + co;
-        if (p.res) {
-          const float* rs = (const float*)p.res + yp * p.res_ld + co;
-          const f32x4 r0 = *(const f32x4*)rs, r1 = *(const f32x4*)(rs + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            w[e] += r0[e];
-            w[4 + e] += r1[e];
-          }
-        }
-        if (p.beta) {
-          const f32x4 r0 = *(const f32x4*)dst, r1 = *(const f32x4*)(dst + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            w[e] += r0[e];
-            w[4 + e] += r1[e];
-          }
-        }
-        for (int k = 0; k < 8; ++k) w[k] = act_f32(w[k], p.act, p.alpha);
-        if (p.dact) {
-          float z[8];
-          unpack8(*(const i32x4*)((const bf16_t*)p.z + yp * p.z_ld + co), z);
-          dact1(w, z, p.dact, p.alpha);
-        }
-        *(f32x4*)dst = f32x4{w[0], w[1], w[2], w[3]};
-        *(f32x4*)(dst + 4) = f32x4{w[4], w[5], w[6], w[7]};
-      } else {
+        epi8_mem<true>(w, p, yp, co);
+      } else {  // operands from the prefetch registers (PRE bits) or from memory
+        if (p.bias) add_f32x8(w, p.bias + co);
         bf16_t* dst = (bf16_t*)p.y + yp * p.y_ld + co;
-        float t[8];
         if (p.res) {
           if constexpr ((PRE & 1) != 0)
-            unpack8(pr_r[(PRE & 1) ? i : 0][j][P], t);
+            add_bf16x8(w, pr_r[i][j][P]);
           else
-            unpack8(*(const i32x4*)((const bf16_t*)p.res + yp * p.res_ld + co), t);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) w[e] += t[e];
+            add_bf16x8(w, *(const i32x4*)((const bf16_t*)p.res + yp * p.res_ld + co));
         }
         if (p.beta) {
           if constexpr ((PRE & 2) != 0)
-            unpack8(pr_b[(PRE & 2) ? i : 0][j][P], t);
+            add_bf16x8(w, pr_b[i][j][P]);
           else
-            unpack8(*(const i32x4*)dst, t);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) w[e] += t[e];
+            add_bf16x8(w, *(const i32x4*)dst);
         }
-        act1(w, p.act, p.alpha);
+        act8(w, p.act, p.alpha);
         if (p.dact) {
           if constexpr ((PRE & 4) != 0)
-            unpack8(pr_z[(PRE & 4) ? i : 0][j][P], t);
+            dact_bf16x8(w, pr_z[i][j][P], p.dact, p.alpha);
           else
-            unpack8(*(const i32x4*)((const bf16_t*)p.z + yp * p.z_ld + co), t);
-          dact1(w, t, p.dact, p.alpha);
+            dact_bf16x8(w, *(const i32x4*)((const bf16_t*)p.z + yp * p.z_ld + co), p.dact, p.alpha);
         }
-        i32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (int)pk_bf16(w[2 * e], w[2 * e + 1]);
+        const i32x4 o = pack_bf16x8(w);
         if constexpr (CE)
           ob[2 * j + P] = o;
         else if (!(dbg & 1) || w[0] == 12345.678f)
@@ -580,16 +491,7 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_persist_kernel(const d
       const int pix = p0 + wp * 32 * MI + 32 * i + r32;
       float v[TMC][2][8];
 #pragma unroll
-      for (int j = 0; j < TMC; ++j)
-#pragma unroll
-        for (int P = 0; P < 2; ++P)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[i][j][8 * P + e]),
-                                                             __float_as_uint(acc[i][j][8 * P + 4 + e]), false, false);
-            v[j][P][e] = __uint_as_float(sw[0]);
-            v[j][P][4 + e] = __uint_as_float(sw[1]);
-          }
+      for (int j = 0; j < TMC; ++j) acc_rows8(acc[i][j], v[j]);
       if (pix >= npix) continue;
       long long yp = pix;
       if (p.osy != 1 || p.osx != 1 || p.ory != 0 || p.orx != 0 || p.yh != p.oh || p.yw != p.ow) {
@@ -604,36 +506,7 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_persist_kernel(const d
         for (int P = 0; P < 2; ++P) {
           const int co = c0 + wc * 32 * TMC + 32 * j + 16 * P + 8 * hh;
           if (co >= p.cout) continue;
-          float* w = v[j][P];
-          if (p.bias) {
-            const f32x4 b0 = *(const f32x4*)(p.bias + co), b1 = *(const f32x4*)(p.bias + co + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[e] += b0[e];
-              w[4 + e] += b1[e];
-            }
-          }
-          bf16_t* dst = (bf16_t*)p.y + yp * p.y_ld + co;
-          float t[8];
-          if (p.res) {
-            unpack8(*(const i32x4*)((const bf16_t*)p.res + yp * p.res_ld + co), t);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) w[e] += t[e];
-          }
-          if (p.beta) {
-            unpack8(*(const i32x4*)dst, t);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) w[e] += t[e];
-          }
-          act1(w, p.act, p.alpha);
-          if (p.dact) {
-            unpack8(*(const i32x4*)((const bf16_t*)p.z + yp * p.z_ld + co), t);
-            dact1(w, t, p.dact, p.alpha);
-          }
-          i32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (int)pk_bf16(w[2 * e], w[2 * e + 1]);
-          *(i32x4*)dst = o;
+          epi8_mem<false>(v[j][P], p, yp, co);
         }
     }
   }
@@ -857,9 +730,7 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_ring_kernel(const dvie
 #pragma unroll
             for (int e = 0; e < 8; ++e) w[e] = fmaxf(w[e], w[e] * p.alpha);  // (0 <= alpha <= 1: launch)
           }
-          i32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (int)pk_bf16(w[2 * e], w[2 * e + 1]);
+          const i32x4 o = pack_bf16x8(w);
           const int co = c0 + wc * 32 * TMC + 32 * j + 16 * P + 8 * hh;
           // (a buffer store that every wave issues, out-of-range lanes aimed past the buffer's
           // range and dropped: the per-wave store count the next wait counts on is uniform)

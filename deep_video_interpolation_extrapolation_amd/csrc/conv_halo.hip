@@ -29,52 +29,17 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "conv_epilogue.h"
 
 namespace dvie {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{a, b}), bf16x2));
-}
 
 __device__ __forceinline__ int xcd_remap3(int b, int nb) {
   const int g = b & 7, i = b >> 3;
   const int q = nb >> 3, r = nb & 7;
   const int start = g < r ? g * (q + 1) : r * (q + 1) + (g - r) * q;
   return start + i;
-}
-
-// F32OUT: the epilogue stores fp32 (e.g. the fp32 head outputs of a bf16 plan): ELU / tanh
-// through expm1f / tanhf; the short v_exp_f32 forms (common.h) are for bf16 stores only
-template <bool F32OUT = false>
-__device__ __forceinline__ void act_apply(float* v, int n, int act, float alpha) {
-  if (act == DVIE_ACT_LRELU) {
-    for (int k = 0; k < n; ++k) v[k] = v[k] > 0.f ? v[k] : v[k] * alpha;
-  } else if (act == DVIE_ACT_RELU) {
-    for (int k = 0; k < n; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
-  } else if (act == DVIE_ACT_ELU) {
-    for (int k = 0; k < n; ++k) v[k] = F32OUT ? (v[k] > 0.f ? v[k] : expm1f(v[k])) : elu_bf(v[k]);
-  } else if (act == DVIE_ACT_TANH) {
-    for (int k = 0; k < n; ++k) v[k] = F32OUT ? tanhf(v[k]) : tanh_bf(v[k]);
-  }
-}
-
-__device__ __forceinline__ void dact_apply(float* v, const float* z, int n, int dact, float alpha) {
-  if (dact == DVIE_ACT_LRELU) {
-    for (int k = 0; k < n; ++k) v[k] *= z[k] > 0.f ? 1.f : alpha;
-  } else if (dact == DVIE_ACT_RELU) {
-    for (int k = 0; k < n; ++k) v[k] = z[k] > 0.f ? v[k] : 0.f;
-  } else if (dact == DVIE_ACT_ELU) {
-    for (int k = 0; k < n; ++k) v[k] *= z[k] > 0.f ? 1.f : z[k] + 1.f;
-  } else if (dact == DVIE_ACT_TANH) {
-    for (int k = 0; k < n; ++k) v[k] *= 1.f - z[k] * z[k];
-  }
 }
 
 template <int TM, int WC, int WP, int TH, int TW>
@@ -463,79 +428,17 @@ __global__ __launch_bounds__(WC* WP * 64) void conv_halo_kernel(const dvie_conv_
           const int co = J.c0 + wc * 32 * TM + 32 * i + 16 * P + 8 * hh - cq;
           if (co + cq >= p.cout) continue;
           float* w = v[P];
-          if (p.bias) {
-            const f32x4 b0 = *(const f32x4*)(p.bias + co), b1 = *(const f32x4*)(p.bias + co + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[e] += b0[e];
-              w[4 + e] += b1[e];
-            }
-          }
           if constexpr (OUTF32) {
-            float* dst = (float*)p.y + pix * p.y_ld + co;
-            if (p.res) {
-              const float* rs = (const float*)p.res + pix * p.res_ld + co;
-              const f32x4 r0 = *(const f32x4*)rs, r1 = *(const f32x4*)(rs + 4);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[e] += r0[e];
-                w[4 + e] += r1[e];
-              }
-            }
-            if (p.beta) {
-              const f32x4 r0 = *(const f32x4*)dst, r1 = *(const f32x4*)(dst + 4);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[e] += r0[e];
-                w[4 + e] += r1[e];
-              }
-            }
-            act_apply<true>(w, 8, p.act, p.alpha);
-            if (p.dact) {
-              float z[8];
-              const i32x4 tz = *(const i32x4*)((const bf16_t*)p.z + pix * p.z_ld + co);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                z[2 * e] = __uint_as_float(((uint32_t)tz[e]) << 16);
-                z[2 * e + 1] = __uint_as_float(((uint32_t)tz[e]) & 0xffff0000u);
-              }
-              dact_apply(w, z, 8, p.dact, p.alpha);
-            }
-            *(f32x4*)dst = f32x4{w[0], w[1], w[2], w[3]};
-            *(f32x4*)(dst + 4) = f32x4{w[4], w[5], w[6], w[7]};
-          } else {
+            epi8_mem<true>(w, p, pix, co);
+          } else {  // operands from the prefetch registers or from memory
+            if (p.bias) add_f32x8(w, p.bias + co);
             bf16_t* dst = (bf16_t*)p.y + pix * p.y_ld + co;
-            if (p.res) {
-              const i32x4 tr = PRE ? pre_r[i][b][P] : *(const i32x4*)((const bf16_t*)p.res + pix * p.res_ld + co);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[2 * e] += __uint_as_float(((uint32_t)tr[e]) << 16);
-                w[2 * e + 1] += __uint_as_float(((uint32_t)tr[e]) & 0xffff0000u);
-              }
-            }
-            if (p.beta) {
-              const i32x4 tr = PRE ? pre_b[i][b][P] : *(const i32x4*)dst;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[2 * e] += __uint_as_float(((uint32_t)tr[e]) << 16);
-                w[2 * e + 1] += __uint_as_float(((uint32_t)tr[e]) & 0xffff0000u);
-              }
-            }
-            act_apply(w, 8, p.act, p.alpha);
-            if (p.dact) {
-              float z[8];
-              const i32x4 tz = PRE ? pre_z[i][b][P] : *(const i32x4*)((const bf16_t*)p.z + pix * p.z_ld + co);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                z[2 * e] = __uint_as_float(((uint32_t)tz[e]) << 16);
-                z[2 * e + 1] = __uint_as_float(((uint32_t)tz[e]) & 0xffff0000u);
-              }
-              dact_apply(w, z, 8, p.dact, p.alpha);
-            }
-            i32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(w[2 * e], w[2 * e + 1]);
-            *(i32x4*)dst = o;
+            if (p.res) add_bf16x8(w, PRE ? pre_r[i][b][P] : *(const i32x4*)((const bf16_t*)p.res + pix * p.res_ld + co));
+            if (p.beta) add_bf16x8(w, PRE ? pre_b[i][b][P] : *(const i32x4*)dst);
+            act8(w, p.act, p.alpha);
+            if (p.dact)
+              dact_bf16x8(w, PRE ? pre_z[i][b][P] : *(const i32x4*)((const bf16_t*)p.z + pix * p.z_ld + co), p.dact, p.alpha);
+            *(i32x4*)dst = pack_bf16x8(w);
           }
         }
       }
@@ -636,80 +539,7 @@ __device__ __forceinline__ void ws_epilogue(const dvie_conv_desc& p, const f32x1
   for (int P = 0; P < 2; ++P) {
     const int co = co8 + 16 * P;
     if (co >= p.cout) continue;
-    float* w = v[P];
-    if (p.bias) {
-      const f32x4 b0 = *(const f32x4*)(p.bias + co), b1 = *(const f32x4*)(p.bias + co + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        w[e] += b0[e];
-        w[4 + e] += b1[e];
-      }
-    }
-    float t8[8];
-    if constexpr (OUTF32) {
-      float* dst = (float*)p.y + pix * p.y_ld + co;
-      if (p.res) {
-        const float* rs = (const float*)p.res + pix * p.res_ld + co;
-        const f32x4 r0 = *(const f32x4*)rs, r1 = *(const f32x4*)(rs + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          w[e] += r0[e];
-          w[4 + e] += r1[e];
-        }
-      }
-      if (p.beta) {
-        const f32x4 r0 = *(const f32x4*)dst, r1 = *(const f32x4*)(dst + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          w[e] += r0[e];
-          w[4 + e] += r1[e];
-        }
-      }
-      act_apply<true>(w, 8, p.act, p.alpha);
-      if (p.dact) {
-        const i32x4 tz = *(const i32x4*)((const bf16_t*)p.z + pix * p.z_ld + co);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          t8[2 * e] = __uint_as_float(((uint32_t)tz[e]) << 16);
-          t8[2 * e + 1] = __uint_as_float(((uint32_t)tz[e]) & 0xffff0000u);
-        }
-        dact_apply(w, t8, 8, p.dact, p.alpha);
-      }
-      *(f32x4*)dst = f32x4{w[0], w[1], w[2], w[3]};
-      *(f32x4*)(dst + 4) = f32x4{w[4], w[5], w[6], w[7]};
-    } else {
-      bf16_t* dst = (bf16_t*)p.y + pix * p.y_ld + co;
-      if (p.res) {
-        const i32x4 tr = *(const i32x4*)((const bf16_t*)p.res + pix * p.res_ld + co);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          w[2 * e] += __uint_as_float(((uint32_t)tr[e]) << 16);
-          w[2 * e + 1] += __uint_as_float(((uint32_t)tr[e]) & 0xffff0000u);
-        }
-      }
-      if (p.beta) {
-        const i32x4 tr = *(const i32x4*)dst;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          w[2 * e] += __uint_as_float(((uint32_t)tr[e]) << 16);
-          w[2 * e + 1] += __uint_as_float(((uint32_t)tr[e]) & 0xffff0000u);
-        }
-      }
-      act_apply(w, 8, p.act, p.alpha);
-      if (p.dact) {
-        const i32x4 tz = *(const i32x4*)((const bf16_t*)p.z + pix * p.z_ld + co);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          t8[2 * e] = __uint_as_float(((uint32_t)tz[e]) << 16);
-          t8[2 * e + 1] = __uint_as_float(((uint32_t)tz[e]) & 0xffff0000u);
-        }
-        dact_apply(w, t8, 8, p.dact, p.alpha);
-      }
-      i32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(w[2 * e], w[2 * e + 1]);
-      *(i32x4*)dst = o;
-    }
+    epi8_mem<OUTF32>(v[P], p, pix, co);
   }
 }
 
@@ -927,37 +757,9 @@ __device__ __forceinline__ void strip_epilogue(const dvie_conv_desc& p, const f3
     const int co = co8 + 16 * P;
     if (co >= p.cout) continue;
     float* w = v[P];
-    if (p.bias) {
-      const f32x4 b0 = *(const f32x4*)(p.bias + co), b1 = *(const f32x4*)(p.bias + co + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        w[e] += b0[e];
-        w[4 + e] += b1[e];
-      }
-    }
-    auto add_bf = [&](const i32x4 t) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        w[2 * e] += __uint_as_float(((uint32_t)t[e]) << 16);
-        w[2 * e + 1] += __uint_as_float(((uint32_t)t[e]) & 0xffff0000u);
-      }
-    };
-    if constexpr ((EPI & 1) != 0) add_bf(er[P]);
-    if constexpr ((EPI & 2) != 0) add_bf(eb[P]);
-    act_apply(w, 8, p.act, p.alpha);
-    if constexpr ((EPI & 4) != 0) {
-      float z[8];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        z[2 * e] = __uint_as_float(((uint32_t)ez[P][e]) << 16);
-        z[2 * e + 1] = __uint_as_float(((uint32_t)ez[P][e]) & 0xffff0000u);
-      }
-      dact_apply(w, z, 8, p.dact, p.alpha);
-    }
-    i32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(w[2 * e], w[2 * e + 1]);
-    *(i32x4*)((bf16_t*)p.y + pix * p.y_ld + co) = o;
+    if (p.bias) add_f32x8(w, p.bias + co);
+    *(i32x4*)((bf16_t*)p.y + pix * p.y_ld + co) =
+        epi8_regs<(EPI & 1) != 0, (EPI & 2) != 0, (EPI & 4) != 0>(w, p, er + P, eb + P, ez + P);
   }
 }
 
@@ -1366,33 +1168,11 @@ __global__ __launch_bounds__(512, 2) void conv_nk_kernel(const dvie_conv_desc p,
 #pragma unroll
         for (int P = 0; P < 2; ++P) {
           float* w = v[P];
-          if (p.res) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[2 * e] += __uint_as_float(((uint32_t)er[b][P][e]) << 16);
-              w[2 * e + 1] += __uint_as_float(((uint32_t)er[b][P][e]) & 0xffff0000u);
-            }
-          }
-          if (p.beta) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[2 * e] += __uint_as_float(((uint32_t)eb[b][P][e]) << 16);
-              w[2 * e + 1] += __uint_as_float(((uint32_t)eb[b][P][e]) & 0xffff0000u);
-            }
-          }
-          act_apply(w, 8, p.act, p.alpha);
-          if (p.dact) {
-            float t8[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              t8[2 * e] = __uint_as_float(((uint32_t)ez[b][P][e]) << 16);
-              t8[2 * e + 1] = __uint_as_float(((uint32_t)ez[b][P][e]) & 0xffff0000u);
-            }
-            dact_apply(w, t8, 8, p.dact, p.alpha);
-          }
-          i32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(w[2 * e], w[2 * e + 1]);
+          if (p.res) add_bf16x8(w, er[b][P]);
+          if (p.beta) add_bf16x8(w, eb[b][P]);
+          act8(w, p.act, p.alpha);
+          if (p.dact) dact_bf16x8(w, ez[b][P], p.dact, p.alpha);
+          const i32x4 o = pack_bf16x8(w);
           unsigned o_y, o_r, o_z;
           offs(cur, b, P, o_y, o_r, o_z);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), ry, o_y, 0, 0);
@@ -1764,41 +1544,8 @@ __global__ __launch_bounds__(512) void conv_h8_kernel(const dvie_conv_desc p, in
           for (int P = 0; P < 2; ++P) {
             const int co = J.c0 + wc * 64 + 32 * i + 16 * P + 8 * hh;
             float* w = v8[P];
-            if (p.bias) {
-              const f32x4 b0 = *(const f32x4*)(p.bias + co), b1 = *(const f32x4*)(p.bias + co + 4);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[e] += b0[e];
-                w[4 + e] += b1[e];
-              }
-            }
-            if (EPI & 1) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[2 * e] += __uint_as_float(((uint32_t)o_r[u][P][e]) << 16);
-                w[2 * e + 1] += __uint_as_float(((uint32_t)o_r[u][P][e]) & 0xffff0000u);
-              }
-            }
-            if (EPI & 2) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[2 * e] += __uint_as_float(((uint32_t)o_b[u][P][e]) << 16);
-                w[2 * e + 1] += __uint_as_float(((uint32_t)o_b[u][P][e]) & 0xffff0000u);
-              }
-            }
-            act_apply(w, 8, p.act, p.alpha);
-            if (EPI & 4) {
-              float z[8];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                z[2 * e] = __uint_as_float(((uint32_t)o_z[u][P][e]) << 16);
-                z[2 * e + 1] = __uint_as_float(((uint32_t)o_z[u][P][e]) & 0xffff0000u);
-              }
-              dact_apply(w, z, 8, p.dact, p.alpha);
-            }
-            i32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(w[2 * e], w[2 * e + 1]);
+            if (p.bias) add_f32x8(w, p.bias + co);
+            const i32x4 o = epi8_regs<(EPI & 1) != 0, (EPI & 2) != 0, (EPI & 4) != 0>(w, p, &o_r[u][P], &o_b[u][P], &o_z[u][P]);
             if (ok) __builtin_amdgcn_raw_buffer_store_b128(o, rb, (unsigned)((dp * p.y_ld + co) * 2), 0, 0);
           }
         }

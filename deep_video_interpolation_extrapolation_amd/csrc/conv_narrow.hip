@@ -23,11 +23,7 @@
 // activation / activation-derivative, fp32 or bf16 output.
 #include <stdlib.h>
 
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "conv_epilogue.h"
 
 namespace dvie {
 
@@ -48,15 +44,6 @@ struct NarrowCfg {
   static constexpr int SMEM = 2 * STAGE;
 };
 static_assert(NarrowCfg::SMEM <= 163840, "two stages fit the LDS");
-
-__device__ __forceinline__ uint32_t pk2_bf16(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{a, b}), bf16x2));
-}
-
-__device__ __forceinline__ void narrow_act(float* v, int act, float alpha) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = act_bf(v[k], act, alpha);
-}
 
 template <bool OUTF32>
 __global__ __launch_bounds__(512) void conv_narrow_kernel(const dvie_conv_desc p, int tiles_x, int tiles_y,
@@ -230,78 +217,7 @@ __global__ __launch_bounds__(512) void conv_narrow_kernel(const dvie_conv_desc p
       for (int P = 0; P < 2; ++P) {
         const int co = 16 * P + 8 * hh;
         if (co >= p.cout) continue;
-        float* w = v[P];
-        if (p.bias) {
-          const f32x4 b0 = *(const f32x4*)(p.bias + co), b1 = *(const f32x4*)(p.bias + co + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            w[e] += b0[e];
-            w[4 + e] += b1[e];
-          }
-        }
-        if constexpr (OUTF32) {
-          float* dst = (float*)p.y + pix * p.y_ld + co;
-          if (p.res) {
-            const float* rs = (const float*)p.res + pix * p.res_ld + co;
-            const f32x4 r0 = *(const f32x4*)rs, r1 = *(const f32x4*)(rs + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[e] += r0[e];
-              w[4 + e] += r1[e];
-            }
-          }
-          if (p.beta) {
-            const f32x4 r0 = *(const f32x4*)dst, r1 = *(const f32x4*)(dst + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[e] += r0[e];
-              w[4 + e] += r1[e];
-            }
-          }
-#pragma unroll
-          for (int k = 0; k < 8; ++k) w[k] = act_f32(w[k], p.act, p.alpha);
-          if (p.dact) {
-            const i32x4 tz = *(const i32x4*)((const bf16_t*)p.z + pix * p.z_ld + co);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[2 * e] *= act_dz(__uint_as_float(((uint32_t)tz[e]) << 16), p.dact, p.alpha);
-              w[2 * e + 1] *= act_dz(__uint_as_float(((uint32_t)tz[e]) & 0xffff0000u), p.dact, p.alpha);
-            }
-          }
-          *(f32x4*)dst = f32x4{w[0], w[1], w[2], w[3]};
-          *(f32x4*)(dst + 4) = f32x4{w[4], w[5], w[6], w[7]};
-        } else {
-          bf16_t* dst = (bf16_t*)p.y + pix * p.y_ld + co;
-          if (p.res) {
-            const i32x4 tr = *(const i32x4*)((const bf16_t*)p.res + pix * p.res_ld + co);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[2 * e] += __uint_as_float(((uint32_t)tr[e]) << 16);
-              w[2 * e + 1] += __uint_as_float(((uint32_t)tr[e]) & 0xffff0000u);
-            }
-          }
-          if (p.beta) {
-            const i32x4 tr = *(const i32x4*)dst;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[2 * e] += __uint_as_float(((uint32_t)tr[e]) << 16);
-              w[2 * e + 1] += __uint_as_float(((uint32_t)tr[e]) & 0xffff0000u);
-            }
-          }
-          narrow_act(w, p.act, p.alpha);
-          if (p.dact) {
-            const i32x4 tz = *(const i32x4*)((const bf16_t*)p.z + pix * p.z_ld + co);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              w[2 * e] *= act_dz(__uint_as_float(((uint32_t)tz[e]) << 16), p.dact, p.alpha);
-              w[2 * e + 1] *= act_dz(__uint_as_float(((uint32_t)tz[e]) & 0xffff0000u), p.dact, p.alpha);
-            }
-          }
-          i32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (int)pk2_bf16(w[2 * e], w[2 * e + 1]);
-          *(i32x4*)dst = o;
-        }
+        epi8_mem<OUTF32>(v[P], p, pix, co);
       }
     }
   }

@@ -29,11 +29,7 @@
 // waves -5%, both -15%.  The 32-B-per-pixel (16-channel) fragment loads cost the address
 // unit ~4x the cycles of whole 128-B lines; wider chunks need a halo that no longer fits
 // double-buffered beside the weight ring.
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "conv_epilogue.h"
 
 namespace dvie {
 
@@ -41,10 +37,6 @@ typedef __attribute__((address_space(3))) void* lds_ptr_s2;
 
 // vmcnt(N) and lgkmcnt(0)
 #define DVIE_S2_VMCNT_LGKM0(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | (((N) >> 4) << 14) | (7 << 4))
-
-__device__ __forceinline__ uint32_t s2_pack(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{a, b}), bf16x2));
-}
 
 template <int TM, int DW>
 struct S2 {
@@ -308,28 +300,12 @@ __global__ __launch_bounds__(64 * (8 + DW)) void conv_s2_kernel(const dvie_conv_
             const int co = J.c0 + wc * 32 * TM + 32 * i + 16 * P + 8 * hh;
             if (co >= p.cout) continue;
             float* w = v8[P];
-            if (p.bias) {
-              const f32x4 b0 = *(const f32x4*)(p.bias + co), b1 = *(const f32x4*)(p.bias + co + 4);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[e] += b0[e];
-                w[4 + e] += b1[e];
-              }
-            }
-            if (EPI & 1) {
-              const i32x4 tr = *(const i32x4*)((const bf16_t*)p.res + pix * p.res_ld + co);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                w[2 * e] += __uint_as_float(((uint32_t)tr[e]) << 16);
-                w[2 * e + 1] += __uint_as_float(((uint32_t)tr[e]) & 0xffff0000u);
-              }
-            }
+            if (p.bias) add_f32x8(w, p.bias + co);
+            if (EPI & 1) add_bf16x8(w, *(const i32x4*)((const bf16_t*)p.res + pix * p.res_ld + co));
+            // (the per-element switch, not act8: its branch-then-loop form spills at TM = 2, 168 VGPRs)
 #pragma unroll
             for (int e = 0; e < 8; ++e) w[e] = act_bf(w[e], p.act, p.alpha);
-            i32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (int)s2_pack(w[2 * e], w[2 * e + 1]);
-            *(i32x4*)((bf16_t*)p.y + pix * p.y_ld + co) = o;
+            *(i32x4*)((bf16_t*)p.y + pix * p.y_ld + co) = pack_bf16x8(w);
           }
         }
     }

@@ -40,14 +40,6 @@ __device__ __forceinline__ Lerp lerp_src(int dst, int in_size, int out_size, int
   return r;
 }
 
-typedef __bf16 ew_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ew_f32x2 __attribute__((ext_vector_type(2)));
-// two floats -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32; = f2bf for every
-// non-NaN input, a quiet NaN for NaN)
-__device__ __forceinline__ uint32_t ew_pack(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((ew_f32x2{a, b}), ew_bf16x2));
-}
-
 // VW-channel vectors (16 B for bf16 x8 / fp32 x4; 8 B for bf16 x4)
 template <typename T, int VW>
 struct VecN;
@@ -64,7 +56,7 @@ struct VecN<bf16_t, 8> {
   __device__ __forceinline__ static void store(bf16_t* p, const float* v) {
     i32x4 r;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = (int)ew_pack(v[2 * k], v[2 * k + 1]);
+    for (int k = 0; k < 4; ++k) r[k] = (int)pack_bf16x2(v[2 * k], v[2 * k + 1]);
     *(i32x4*)p = r;
   }
 };

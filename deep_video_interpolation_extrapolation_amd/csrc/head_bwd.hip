@@ -28,9 +28,6 @@
 
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 hb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float hb_f32x2 __attribute__((ext_vector_type(2)));
 
 namespace dvie {
 
@@ -72,10 +69,6 @@ __device__ __forceinline__ bf16x8 hb_tr_pair(const char* p0, const char* p1) {
   typedef short s16x8 __attribute__((ext_vector_type(8)));
   const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
   return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ uint32_t hb_pack(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((hb_f32x2{a, b}), hb_bf16x2));
 }
 
 // s_waitcnt vmcnt(n) for a wave-uniform n < 32 (the DMA is inline asm: the compiler counts
@@ -288,15 +281,7 @@ __global__ __launch_bounds__(512) void head3_bwd_kernel(const dvie_head3_bwd_des
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       float v[2][8];
-#pragma unroll
-      for (int P = 0; P < 2; ++P)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc1[b][8 * P + e]),
-                                                           __float_as_uint(acc1[b][8 * P + 4 + e]), false, false);
-          v[P][e] = __uint_as_float(sw[0]);
-          v[P][4 + e] = __uint_as_float(sw[1]);
-        }
+      acc_rows8(acc1[b], v);
       const int px = wr * 64 + 32 * b + r32;  // pixel within the tile
       const int ox = T.x0 + 32 * b + r32;
       const bool in = oy < p.hgt && ox < p.wid;
@@ -315,7 +300,7 @@ __global__ __launch_bounds__(512) void head3_bwd_kernel(const dvie_head3_bwd_des
         }
         i32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (int)hb_pack(w[2 * e], w[2 * e + 1]);
+        for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(w[2 * e], w[2 * e + 1]);
         __builtin_amdgcn_raw_buffer_store_b128(
             o, rdh, in ? (unsigned)((pix * p.dh_ld + cb * 64 + 8 * c8) * 2) : OOB, 0, 0);
       }

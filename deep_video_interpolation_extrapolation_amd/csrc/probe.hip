@@ -5,7 +5,6 @@
 // is the MFMA ceiling the conv kernels can approach on the same box.
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace dvie {
 

@@ -23,9 +23,6 @@
 
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 se_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float se_f32x2 __attribute__((ext_vector_type(2)));
 
 namespace dvie {
 
@@ -51,10 +48,6 @@ struct SeCfg {
   static constexpr int SMEM = O_E2 + E2_SZ;
 };
 static_assert(SeCfg::SMEM <= 163840, "segenc LDS");
-
-__device__ __forceinline__ uint32_t se_pack(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((se_f32x2{a, b}), se_bf16x2));
-}
 
 // One conv stage over a flattened region of `npx` pixels of width RW: output pixel q = (r, c)
 // reads the source region (width RW + 2, pitch SP, CPT 16-B chunks per pixel) at (r + i, c + j).
@@ -227,7 +220,7 @@ __global__ __launch_bounds__(512) void segenc_fwd_kernel(const dvie_segenc_desc 
             for (int e = 0; e < 4; ++e) {
               const float a = in ? elu_bf(v[P][2 * e] + bb0[P][2 * e]) : 0.f;
               const float b = in ? elu_bf(v[P][2 * e + 1] + bb0[P][2 * e + 1]) : 0.f;
-              o[e] = (int)se_pack(a, b);
+              o[e] = (int)pack_bf16x2(a, b);
             }
             *(i32x4*)(smem + C::O_E1 + (r * C::E1_W + c) * C::E_PITCH + co * 2) = o;
             if (interior) *(i32x4*)((bf16_t*)p.e1 + ((long long)(n * p.h + gy) * p.w + gx) * p.e1_ld + co) = o;
@@ -248,7 +241,7 @@ __global__ __launch_bounds__(512) void segenc_fwd_kernel(const dvie_segenc_desc 
             for (int e = 0; e < 4; ++e) {
               const float a = in ? elu_bf(v[P][2 * e] + bb2[P][2 * e]) : 0.f;
               const float b = in ? elu_bf(v[P][2 * e + 1] + bb2[P][2 * e + 1]) : 0.f;
-              o[e] = (int)se_pack(a, b);
+              o[e] = (int)pack_bf16x2(a, b);
             }
             *(i32x4*)(smem + C::O_E2 + (r * C::E2_W + c) * C::E_PITCH + co * 2) = o;
             if (interior) *(i32x4*)((bf16_t*)p.e2 + ((long long)(n * p.h + gy) * p.w + gx) * p.e2_ld + co) = o;
@@ -262,7 +255,7 @@ __global__ __launch_bounds__(512) void segenc_fwd_kernel(const dvie_segenc_desc 
           if (hh || gy >= p.h || gx >= p.w) return;  // channels 0..7 = pair 0, lane half 0
           i32x4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (int)se_pack(v[0][2 * e] + bb4[2 * e], v[0][2 * e + 1] + bb4[2 * e + 1]);
+          for (int e = 0; e < 4; ++e) o[e] = (int)pack_bf16x2(v[0][2 * e] + bb4[2 * e], v[0][2 * e + 1] + bb4[2 * e + 1]);
           *(i32x4*)((bf16_t*)p.out + ((long long)(n * p.h + gy) * p.w + gx) * p.out_ld) = o;
         });
   }
@@ -318,13 +311,12 @@ __device__ __forceinline__ bf16x8 hb_tr_pair_se(const char* p0, const char* p1) 
 
 // t + the sum of a fragment's 8 bf16 values, in fp32 (four v_dot2c_f32_bf16 against (1, 1))
 __device__ __forceinline__ float sum8_bf16_se(const bf16x8 v, float t) {
-  typedef __bf16 bf16x2_se __attribute__((ext_vector_type(2)));
   const i32x4 u = __builtin_bit_cast(i32x4, v);
-  const bf16x2_se one = __builtin_bit_cast(bf16x2_se, 0x3F803F80);
+  const bf16x2 one = __builtin_bit_cast(bf16x2, 0x3F803F80);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int w = u[e];
-    t = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_se, w), one, t, false);
+    t = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, w), one, t, false);
   }
   return t;
 }
@@ -617,7 +609,7 @@ __global__ __launch_bounds__(512) void segenc_bwd_kernel(const dvie_segenc_bwd_d
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float za = __uint_as_float(((uint32_t)z[e]) << 16), zb = __uint_as_float(((uint32_t)z[e]) & 0xffff0000u);
-            o[e] = (int)se_pack(in ? v[2 * e] * act_dz(za, DVIE_ACT_ELU, 0.f) : 0.f,
+            o[e] = (int)pack_bf16x2(in ? v[2 * e] * act_dz(za, DVIE_ACT_ELU, 0.f) : 0.f,
                                 in ? v[2 * e + 1] * act_dz(zb, DVIE_ACT_ELU, 0.f) : 0.f);
           }
           if (q[b] < NPX) *(i32x4*)(smem + C::O_D2 + sw64(q[b], ch)) = o;
@@ -681,7 +673,7 @@ __global__ __launch_bounds__(512) void segenc_bwd_kernel(const dvie_segenc_bwd_d
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float za = __uint_as_float(((uint32_t)z[e]) << 16), zb = __uint_as_float(((uint32_t)z[e]) & 0xffff0000u);
-          o[e] = (int)se_pack(in ? v[2 * e] * act_dz(za, DVIE_ACT_ELU, 0.f) : 0.f,
+          o[e] = (int)pack_bf16x2(in ? v[2 * e] * act_dz(za, DVIE_ACT_ELU, 0.f) : 0.f,
                               in ? v[2 * e + 1] * act_dz(zb, DVIE_ACT_ELU, 0.f) : 0.f);
         }
         *(i32x4*)(smem + C::O_D1 + sw64(q, ch)) = o;

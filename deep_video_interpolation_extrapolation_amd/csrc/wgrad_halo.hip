@@ -24,7 +24,6 @@
 
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace dvie {
 
@@ -40,14 +39,13 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* p0, const char* p1) {
 
 // t + the sum of a fragment's 8 bf16 values, in fp32: four v_dot2c_f32_bf16 against (1, 1)
 // (bias column sums)
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float sum8_bf16(const bf16x8 v, float t) {
   const i32x4 u = __builtin_bit_cast(i32x4, v);
-  const bf16x2_t one = __builtin_bit_cast(bf16x2_t, 0x3F803F80);
+  const bf16x2 one = __builtin_bit_cast(bf16x2, 0x3F803F80);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int w = u[e];  // (a bit_cast of the vector element itself reads element 0 on this compiler)
-    t = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, w), one, t, false);
+    t = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, w), one, t, false);
   }
   return t;
 }

@@ -172,6 +172,21 @@ def test_conv_strip_fp32_out(dev, mode, strip, monkeypatch):
     assert err < 1e-2, (mode, strip, err)
 
 
+F32_OUT_SHAPES = [  # the shared fp32-output epilogue outside the strip / ws / narrow kernels
+    (1, 9, 40, 128, 128, 3),    # chunked halo, 128-channel tile, ragged rows and columns, too few tiles for h8
+    (1, 9, 40, 64, 96, 1),      # 1x1 single K-step, partial channel tile, ragged pixel count
+]
+
+
+@pytest.mark.parametrize("mode", ["none", "res+beta+z"])
+@pytest.mark.parametrize("shape", F32_OUT_SHAPES)
+def test_conv_fp32_out_halo_1x1(dev, shape, mode):
+    """fp32 output (fp32 residual and accumulate target) on the chunked halo kernel and the 1x1
+    kernel: the same epilogue the strip / ws / narrow kernels use, same bar."""
+    err = _run(dev, shape, mode, out_f32=True)
+    assert err < 1e-2, (shape, mode, err)
+
+
 H8_SHAPES = [  # 3x3, c % 32 == 0, cout % 128 == 0, >= 224 eight-row tiles: conv_h8_kernel
     (4, 125, 250, 128, 128, 3),   # ragged rows and columns, one tile per workgroup
     (8, 61, 120, 256, 256, 3),    # two 128-channel tiles per pixel tile, 8 chunks
