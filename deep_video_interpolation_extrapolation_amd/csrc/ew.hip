@@ -726,6 +726,25 @@ __global__ __launch_bounds__(256) void ew_nchw_kernel(const dvie_ew_desc p) {
   }
 }
 
+// EW_LABELS: one-hot of a uint8 label map, VW channels of one pixel per thread (the ew_kernel
+// mapping: a wave's stores are one contiguous run).  The cq threads of a pixel read the same
+// label byte; a pixel costs 1 B read against c * sizeof(T) written.
+template <typename T, int VW>
+__global__ __launch_bounds__(256) void ew_labels_kernel(const dvie_ew_desc p, int cq) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= p.w * cq) return;
+  const int x = e / cq;
+  const int c = (e - x * cq) * VW;
+  const int row = blockIdx.y;
+  const int n = row / p.h, y = row - (row / p.h) * p.h;
+  const uint8_t* lab = (const uint8_t*)p.ext;
+  const int l = lab[(long long)n * p.sn + (long long)y * p.sh + (long long)x * p.sw];
+  float v[VW];
+#pragma unroll
+  for (int k = 0; k < VW; ++k) v[k] = (c + k < p.ext_c && l == c + k) ? 1.f : 0.f;
+  VecN<T, VW>::store((T*)p.y + ((long long)row * p.w + x) * p.y_ld + c, v);
+}
+
 }  // namespace dvie
 
 using namespace dvie;
@@ -761,8 +780,11 @@ extern "C" int dvie_ew(const dvie_ew_desc* d, void* stream) {
   DVIE_CHECK_ARG(d->op == DVIE_EW_TONCHW || (d->y && d->y_ld % 4 == 0), "ew: y");
   if (d->op == DVIE_EW_POOL) DVIE_CHECK_ARG(d->sh0 == 2 * d->h && d->sw0 == 2 * d->w, "ew: pool shape");
   if (d->op == DVIE_EW_POOLT) DVIE_CHECK_ARG(d->h == 2 * d->sh0 && d->w == 2 * d->sw0, "ew: poolT shape");
-  if (d->op == DVIE_EW_NCHW || d->op == DVIE_EW_TONCHW || d->op == DVIE_EW_MASK)
+  if (d->op == DVIE_EW_NCHW || d->op == DVIE_EW_TONCHW || d->op == DVIE_EW_MASK || d->op == DVIE_EW_LABELS)
     DVIE_CHECK_ARG(d->ext != nullptr, "ew: ext");
+  if (d->op == DVIE_EW_LABELS)
+    DVIE_CHECK_ARG(d->ext_c > 0 && d->ext_c <= 256 && !d->res && !d->beta && !d->act && !d->dact,
+                   "ew: labels ext_c=%d (1..256), no epilogue operands", d->ext_c);
   if (d->dact) DVIE_CHECK_ARG(d->z != nullptr && d->z_ld % 4 == 0, "ew: z");
   if (d->op == DVIE_EW_IM2COL)
     DVIE_CHECK_ARG(d->ext_c > 0 && d->ext_c % 8 == 0 && d->src0 && d->src_ld0 >= d->ext_c &&
@@ -777,6 +799,15 @@ extern "C" int dvie_ew(const dvie_ew_desc* d, void* stream) {
   const int vw = v8 ? 8 : 4;
   const int cq = d->c / vw;
   const dim3 grid((unsigned)((d->w * cq + 255) / 256), (unsigned)(d->n * d->h));
+  if (d->op == DVIE_EW_LABELS) {
+    if (d->dtype == DVIE_BF16 && v8)
+      DVIE_LAUNCH((ew_labels_kernel<bf16_t, 8>), grid, dim3(256), 0, s, *d, cq);
+    else if (d->dtype == DVIE_BF16)
+      DVIE_LAUNCH((ew_labels_kernel<bf16_t, 4>), grid, dim3(256), 0, s, *d, cq);
+    else
+      DVIE_LAUNCH((ew_labels_kernel<float, 4>), grid, dim3(256), 0, s, *d, cq);
+    DVIE_RETURN_LAUNCH();
+  }
   if (d->dtype == DVIE_BF16) {
     if (v8) {
       // (pairs need every source at most the output's size: a source step <= 1 per pixel)

@@ -819,6 +819,8 @@ size_t dvie_abi_sizeof(int which) {
     case 101: return sizeof(dvie_softmax_desc);
     case 102: return sizeof(dvie_sn_layer);
     case 103: return sizeof(dvie_clip_desc);
+    case 104: return sizeof(dvie_synth_load_desc);
+    case 105: return sizeof(dvie_synth_finish_desc);
     default: return 0;
   }
 }

@@ -342,6 +342,16 @@ class InputOp(_Op):
         return []
 
 
+class LabelInputOp(InputOp):
+    """uint8 label map (n, H, W) of frame `frame` -> its one-hot over the first n_classes
+    channels of an NHWC region (DVIE_EW_LABELS): the values InputOp writes from the fp32
+    one-hot, read at 1 byte per pixel.  Labels >= n_classes give an all-zero pixel."""
+
+    def __init__(self, out, key, frame, n_classes):
+        super().__init__(out, key, None, 0, n_classes, False, False)
+        self.frame = frame
+
+
 class L1FeatOp(_Op):
     """mean |f(pred) - f(gt)| of a feature buffer holding [pred batch | gt batch]."""
 
@@ -426,6 +436,12 @@ class Graph:
         assert not (requires_grad and part == 1)
         op = InputOp(out, key, part, ext_c0, out.c if ext_c is None else ext_c, normalize, requires_grad)
         self._add(op)
+        return out
+
+    def input_labels(self, out, key, frame, n_classes=20):
+        """input `key`, frame `frame`, given as a uint8 label map (Plan.set_input_labels)"""
+        assert 0 < n_classes <= min(out.c, 256), (n_classes, out.c)
+        self._add(LabelInputOp(out, key, frame, n_classes))
         return out
 
     def conv(self, x, module, out, act=L.ACT_NONE, res=None, cmap=None, trainable=True, name=""):
@@ -553,15 +569,127 @@ class Graph:
             r.buf.consumers.append((op, r))
 
     # ---------------- compile ----------------
-    def compile(self, n_fwd, device, n_bwd=None, backward=True):
-        return Plan(self, n_fwd, n_fwd if n_bwd is None else n_bwd, device, backward)
+    def compile(self, n_fwd, device, n_bwd=None, backward=True, alias=False):
+        """alias=True (forward-only plans): the internal buffers are views into one arena,
+        two buffers sharing bytes when no launch needs both (assign_offsets)."""
+        return Plan(self, n_fwd, n_fwd if n_bwd is None else n_bwd, device, backward, alias)
+
+
+# ---------------- arena allocation of forward-only plans ----------------
+ARENA_ALIGN = 512  # the torch caching allocator's block granule: offsets keep its alignment
+
+
+def segenc_fusable(dtype, nf, ops):
+    """whether three ConvOps (Graph.segenc_chain) run as one dvie_segenc_fwd launch in a plan
+    of `nf` images and compute dtype `dtype`"""
+    if dtype != torch.bfloat16 or os.environ.get("DVIE_SEGENC_FUSED", "1") == "0":
+        return False
+    o0, o1, o2 = ops
+    acts = (L.ACT_ELU, L.ACT_ELU, L.ACT_NONE)
+    chans = ((24, 32), (32, 32), (32, 8))
+    for op, act, (ci, co) in zip(ops, acts, chans):
+        lay = op.layer
+        if not (isinstance(op, ConvOp) and op.act == act and op.res is None and lay.kh == 3 and lay.kw == 3
+                and lay.stride == 1 and lay.pad == 1 and lay.dil == 1 and lay.has_bias and op.x.c == ci
+                and op.out.c == co and lay.cout_p == co):
+            return False
+    if not (o1.x.buf is o0.out.buf and o2.x.buf is o1.out.buf and o0.out.c0 == 0 and o1.out.c0 == 0):
+        return False
+    if o0.out.buf.C != 32 or o1.out.buf.C != 32 or o2.out.buf.external:
+        return False
+    x = o0.x
+    return nf * x.H * x.W * x.buf.C * 2 < 0xFFFFFF00
+
+
+def forward_launches(g, nf):
+    """The forward list of graph `g` at batch `nf` as groups of graph ops, one group per
+    launch site: [op] for an op lowered on its own (a ConvTOp's stride phases count as one
+    site: they read and write the same buffers), the three ConvOps of a segmentation encoder
+    where they run as one fused launch."""
+    fused_first, skip = {}, set()
+    if os.environ.get("DVIE_SEGENC_FWD", "1") == "1":
+        for chain in getattr(g, "segenc", []):
+            if segenc_fusable(g.dtype, nf, chain):
+                fused_first[id(chain[0])] = chain
+                skip.update(id(op) for op in chain[1:])
+    return [list(fused_first.get(id(op), (op,))) for op in g.ops if id(op) not in skip]
+
+
+def _op_regions(op):
+    """every region an op reads or writes"""
+    rs = list(op.inputs())
+    for r in (getattr(op, "out", None), getattr(op, "region", None)):  # (region: OutNCHWOp's source)
+        if r is not None:
+            rs.append(r)
+    return rs
+
+
+def forward_lifetimes(g, nf):
+    """{id(buffer): (first, last)} over the launch sites of forward_launches: a buffer is
+    live from the first launch that touches it to the last one (closed interval).  Every
+    buffer a fused launch touches is live across it; a buffer written region by region (the
+    stem concat, the 448-channel concat) lives from its first writer to its last reader."""
+    life = {}
+    for i, ops in enumerate(forward_launches(g, nf)):
+        for op in ops:
+            for r in _op_regions(op):
+                a, b = life.get(id(r.buf), (i, i))
+                life[id(r.buf)] = (min(a, i), max(b, i))
+    return life
+
+
+def assign_offsets(items):
+    """items: [(bytes, first, last)] -> (offsets, arena_bytes): byte offsets, multiples of
+    ARENA_ALIGN, such that two items whose closed intervals [first, last] intersect never
+    share a byte.  Greedy by size: the items in decreasing size (ties: earlier first), each
+    at the lowest offset free of the already placed items it overlaps in time.  Sizes are
+    rounded up to ARENA_ALIGN (as the allocator rounds each block), so arena_bytes <= the sum
+    of the rounded sizes: a layout that would exceed it falls back to one slot per item."""
+    size = [rup(max(int(b), 1), ARENA_ALIGN) for b, _, _ in items]
+    order = sorted(range(len(items)), key=lambda i: (-size[i], items[i][1], i))
+    offsets = [0] * len(items)
+    placed = []
+    arena = 0
+    for i in order:
+        _, f, l = items[i]
+        busy = sorted((offsets[j], offsets[j] + size[j]) for j in placed if items[j][1] <= l and f <= items[j][2])
+        off = 0
+        for lo, hi in busy:
+            if off + size[i] <= lo:
+                break
+            off = max(off, hi)
+        offsets[i] = off
+        placed.append(i)
+        arena = max(arena, off + size[i])
+    if arena > sum(size):
+        offsets, arena = [], 0
+        for sz in size:
+            offsets.append(arena)
+            arena += sz
+    return offsets, arena
+
+
+def arena_layout(g, nf):
+    """Arena layout of the forward of graph `g` at batch `nf`, without allocating: (offsets
+    {id(buffer): byte offset} of the internal buffers, arena_bytes, unaliased_bytes = what one
+    allocation per buffer holds)."""
+    life = forward_lifetimes(g, nf)
+    n_sites = max([b for _, b in life.values()] + [0])
+    bufs = [b for b in g.buffers if not b.external]
+    items = []
+    for b in bufs:
+        nbytes = nf * b.H * b.W * b.C * elem_size(b.dtype or g.dtype)
+        items.append((nbytes,) + life.get(id(b), (0, n_sites)))  # (untouched: kept apart from everything)
+    offsets, arena = assign_offsets(items)
+    return {id(b): o for b, o in zip(bufs, offsets)}, arena, sum(it[0] for it in items)
 
 
 class Plan:
     """Allocated buffers + forward/backward descriptor lists of one graph and shape."""
 
-    def __init__(self, g, nf, nb, device, backward):
-        self.g, self.nf, self.nb, self.device = g, nf, nb, device
+    def __init__(self, g, nf, nb, device, backward, alias=False):
+        assert not (alias and backward), "alias=True is for forward-only plans (a backward reads every activation)"
+        self.g, self.nf, self.nb, self.device, self.alias = g, nf, nb, device, alias
         self.dtype = g.dtype
         self.dt = dv_dtype(g.dtype)
         self.es = elem_size(g.dtype)
@@ -586,18 +714,36 @@ class Plan:
         self._build_forward()
         if backward:
             self._build_backward()
+        # (aliasing orders buffer reuse by the one stream the forward list runs on: only the
+        # weight gradients use the weight lane)
+        assert all(o.lane == 0 for o in self.fwd), "forward ops run on the caller's stream"
         self._finalize()
 
     # ---------------- allocation ----------------
     def _alloc(self):
         g = self.g
+        offsets, self.arena_bytes, self.unaliased_bytes = arena_layout(g, self.nf) if self.alias else ({}, None, 0)
+        if self.alias:
+            # One allocation; every buffer starts on an ARENA_ALIGN boundary, as its own
+            # torch.empty would (conv_s2 and the 16-byte pointwise paths select on alignment).
+            # Each slot keeps the allocator's rounding of its size.  No forward kernel is known to
+            # read past that: the DMA kernels (halo, 1x1, stride-2, narrow, segenc) bound their
+            # reads by exact buffer ranges and the pointwise ones stay inside c channels; a read
+            # past a slot would land in another slot of the arena, not outside it.
+            self.arena = torch.empty(max(self.arena_bytes, ARENA_ALIGN), dtype=torch.uint8, device=self.device)
+            self.keep.append(self.arena)
         for b in g.buffers:
             dt = b.dtype or self.dtype
             b.dt = dt
             if b.external:
                 b.t = None
+            elif self.alias:
+                nbytes = self.nf * b.H * b.W * b.C * elem_size(dt)
+                o = offsets[id(b)]
+                b.t = self.arena[o:o + nbytes].view(dt).view(self.nf, b.H, b.W, b.C)
             else:
                 b.t = torch.empty((self.nf, b.H, b.W, b.C), dtype=dt, device=self.device)
+                self.unaliased_bytes += b.t.numel() * b.t.element_size()
         # gradient requirements
         if self.backward_enabled:
             for op in g.ops:
@@ -807,23 +953,7 @@ class Plan:
 
     # ---------------- forward ----------------
     def _segenc_fusable(self, ops):
-        if self.dtype != torch.bfloat16 or os.environ.get("DVIE_SEGENC_FUSED", "1") == "0":
-            return False
-        o0, o1, o2 = ops
-        acts = (L.ACT_ELU, L.ACT_ELU, L.ACT_NONE)
-        chans = ((24, 32), (32, 32), (32, 8))
-        for op, act, (ci, co) in zip(ops, acts, chans):
-            lay = op.layer
-            if not (isinstance(op, ConvOp) and op.act == act and op.res is None and lay.kh == 3 and lay.kw == 3
-                    and lay.stride == 1 and lay.pad == 1 and lay.dil == 1 and lay.has_bias and op.x.c == ci
-                    and op.out.c == co and lay.cout_p == co):
-                return False
-        if not (o1.x.buf is o0.out.buf and o2.x.buf is o1.out.buf and o0.out.c0 == 0 and o1.out.c0 == 0):
-            return False
-        if o0.out.buf.C != 32 or o1.out.buf.C != 32 or o2.out.buf.external:
-            return False
-        x = o0.x
-        return self.nf * x.H * x.W * x.buf.C * 2 < 0xFFFFFF00
+        return segenc_fusable(self.dtype, self.nf, ops)
 
     def _segenc_fwd(self, ops):
         o0, o1, o2 = ops
@@ -845,22 +975,20 @@ class Plan:
     def _build_forward(self):
         g = self.g
         nf = self.nf
-        fused_first, skip = {}, set()
         # the fused forward (one dvie_segenc_fwd per encoder) is the default since its stages
         # run two 32-pixel blocks per wave: 0.316 vs 0.344 ms per step for the three convs at
         # 8x256x512 (profiles/r06/segenc_*); DVIE_SEGENC_FWD=0 runs the three convs
-        fwd_on = os.environ.get("DVIE_SEGENC_FWD", "1") == "1"
-        for chain in getattr(g, "segenc", []) if fwd_on else []:
-            if self._segenc_fusable(chain):
-                fused_first[id(chain[0])] = chain
-                skip.update(id(op) for op in chain[1:])
-        for op in g.ops:
-            if id(op) in skip:
+        for site in forward_launches(g, nf):
+            op = site[0]
+            if len(site) > 1:
+                self.fwd.append(self._segenc_fwd(tuple(site)))
                 continue
-            if id(op) in fused_first:
-                self.fwd.append(self._segenc_fwd(fused_first[id(op)]))
-                continue
-            if isinstance(op, InputOp):
+            if isinstance(op, LabelInputOp):
+                o = self.ew_desc(L.EW_LABELS, nf, op.out.H, op.out.W, op.out.c, self.ptr(op.out), op.out.buf.C)
+                o.u.ew.ext_c = op.ext_c
+                self.ext_in.setdefault(op.key, []).append((len(self.fwd), op))
+                self.fwd.append(o)
+            elif isinstance(op, InputOp):
                 n0, cnt = self._part(op.part)
                 o = self.ew_desc(L.EW_NCHW, cnt, op.out.H, op.out.W, op.out.c, self.ptr(op.out, n0), op.out.buf.C)
                 o.u.ew.ext_c = op.ext_c
@@ -1956,10 +2084,23 @@ class Plan:
         self.n_bwd = len(self.bwd)
 
     # ---------------- execution ----------------
+    def set_input_labels(self, key, parts):
+        """Patch the label-map input `key` (Graph.input_labels): parts[k] is frame k's uint8
+        (n, H, W) tensor (any strides), read in place."""
+        for idx, op in self.ext_in[key]:
+            assert isinstance(op, LabelInputOp), f"input {key} is not a label input"
+            t = parts[op.frame]
+            assert t.dtype == torch.uint8 and t.device.type == self.device.type
+            assert tuple(t.shape) == (self.nf, op.out.H, op.out.W), (key, tuple(t.shape), self.nf)
+            d = self.fwd_arr[idx + self.fwd_off].u.ew
+            d.ext = t.data_ptr()
+            (d.sn, d.sh, d.sw), d.sc = t.stride(), 0
+
     def set_input(self, key, t):
         """Patch the external NCHW fp32 input `t` (any strides) into the forward list."""
         assert t.dtype == torch.float32 and t.device.type == self.device.type
         for idx, op in self.ext_in[key]:
+            assert not isinstance(op, LabelInputOp), f"input {key} takes label maps (set_input_labels)"
             d = self.fwd_arr[idx + self.fwd_off].u.ew
             assert t.shape[0] == self._part(op.part)[1], (key, tuple(t.shape), self.nf)
             assert t.shape[2:] == (op.out.H, op.out.W) and t.shape[1] >= op.ext_c0 + op.ext_c, (key, tuple(t.shape))
@@ -2200,6 +2341,7 @@ class Plan:
         kinds = {}
         for o in list(self.fwd) + list(self.bwd):
             kinds[o.kind] = kinds.get(o.kind, 0) + 1
-        return dict(n_fwd=len(self.fwd) + 1, n_bwd=self.n_bwd, kinds=kinds, ws_mb=self.ws_floats * 4 / 2**20)
+        return dict(n_fwd=len(self.fwd) + 1, n_bwd=self.n_bwd, kinds=kinds, ws_mb=self.ws_floats * 4 / 2**20,
+                    arena_bytes=self.arena_bytes, unaliased_bytes=self.unaliased_bytes)
 
 

@@ -277,7 +277,7 @@ class HRNet(FlatParams, nn.Module):
         """parameters the HRNet plan writes gradients for"""
         return self._flat_params
 
-    def _lower(self, g, H, W, dry=False, xgrad=False, vgrad=False):
+    def _lower(self, g, H, W, dry=False, xgrad=False, vgrad=False, labels=False):
         A = L
         g.dry = dry
         rup = E.rup
@@ -287,7 +287,10 @@ class HRNet(FlatParams, nn.Module):
         feat = g.buffer("feat", H, W, stem_c)
         for k in range(F):
             s_in = g.buffer(f"seg{k}_in", H, W, 24)
-            g.input_nchw(E.R(s_in), "seg", ext_c0=20 * k, ext_c=20)
+            if labels:  # frame k's uint8 label map, one-hot on the fly (forward-only plans)
+                g.input_labels(E.R(s_in), "seg", frame=k, n_classes=self.n_classes)
+            else:
+                g.input_nchw(E.R(s_in), "seg", ext_c0=20 * k, ext_c=20)
             e1 = g.buffer(f"seg{k}_e1", H, W, 32)
             g.conv(E.R(s_in), self.seg_encoder[0], E.R(e1), act=A.ACT_ELU, name="seg_encoder.0")
             e2 = g.buffer(f"seg{k}_e2", H, W, 32)
@@ -481,13 +484,18 @@ class HRNet(FlatParams, nn.Module):
         g.output("segout", E.R(seg), self.seg_out_dim)
 
     def _build_plan(self, key):
-        n, H, W, dtype, train, dev, xgrad, export = key
+        # an optional ninth component holds the inference flags of a forward-only plan:
+        # "labels" (the segmentations come as uint8 label maps, Plan.set_input_labels) and
+        # "alias" (arena allocation, engine.assign_offsets); synth.py asks for both
+        n, H, W, dtype, train, dev, xgrad, export = key[:8]
+        flags = tuple(key[8]) if len(key) > 8 else ()
+        assert not (train and flags), "label inputs and arena allocation are for forward-only plans"
         self._export_stem = export
         try:
-            g = self._lower(E.Graph(dtype), H, W, xgrad=xgrad, vgrad=bool(train))
+            g = self._lower(E.Graph(dtype), H, W, xgrad=xgrad, vgrad=bool(train), labels="labels" in flags)
         finally:
             self._export_stem = False
-        return g.compile(n, dev, backward=train)
+        return g.compile(n, dev, backward=train, alias="alias" in flags)
 
     # set by InterRefineNet / InterStage3Net: every forward also writes the detached stem
     # features [frames (3F), seg_encoder(seg_k) (4 each)] to `last_stem` (B, 7F, H, W)

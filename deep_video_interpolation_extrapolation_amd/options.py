@@ -8,6 +8,8 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
                             optional val_imgs / val_segs) kept in HBM and prepared on the GPU
                             by data.DeviceClips (train: flip + pseudo-motion crop to input_h x
                             input_w; val: whole frames)
+  --synth_levels K          --split test, INTER: frame-rate doublings of the recursive
+                            interpolation (K levels: 2**K - 1 new frames between two inputs)
 """
 import argparse
 
@@ -61,6 +63,7 @@ GLOBAL = [
     ("--precision", "precision", str, "fp32", ["fp32", "bf16"]),
     ("--synthetic", "synthetic", int, 0, None),
     ("--clip_store", "clip_store", str, None, None),
+    ("--synth_levels", "synth_levels", int, 1, None),
 ]
 
 # second-stage flags of the reference's INTER sub-command (options/options.py:296-380);

@@ -164,6 +164,10 @@ class ExtraTrainer(InterTrainer):
             self._scalars("val/score", res)
         return res
 
+    def _synthesize(self, syn, frames, labels):
+        """--split test, extrapolation: --num_pred_step frames after the clip's last two"""
+        return syn.extrapolate(frames[:, -2:], labels[:, -2:], steps=getattr(self.args, "num_pred_step", 1))
+
     def save_checkpoint(self):
         return super().save_checkpoint()
 

@@ -348,6 +348,43 @@ class InterTrainer:
                     save_image(lst[k].squeeze(0), os.path.join(d, names[k] + ".png"))
         return root
 
+    def _synthesize(self, syn, frames, labels):
+        """--split test, interpolation: --synth_levels frame-rate doublings of the whole clip"""
+        return syn.interpolate(frames, labels, levels=getattr(self.args, "synth_levels", 1))
+
+    def test(self):
+        """--split test: for each clip directory under --cycgen_load_dir/rgb (and /seg, the same
+        file names), all PNGs in sorted order -> synth.VideoSynthesizer on the device (INTER:
+        interpolate with --synth_levels; EXTRA: extrapolate --num_pred_step frames from the
+        last two) -> <cycgen_load_dir>/synth/{rgb,seg,vis_seg}/<clip>/NNNN.png: the frames, the
+        label maps and their palette colouring, numbered in output order."""
+        import numpy as np
+        from PIL import Image
+        from ..synth import VideoSynthesizer
+        from ..utils.net_utils import CITYSCAPES_COLORS
+        a = self.args
+        assert self.rank == 0, "test runs on one worker"
+        assert a.cycgen_load_dir is not None, "please specify --cycgen_load_dir"
+        syn = VideoSynthesizer(self.model.module, max_batch=max(1, a.batch_size))
+        img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
+        root = os.path.join(a.cycgen_load_dir, "synth")
+        palette = np.array(CITYSCAPES_COLORS, dtype=np.uint8)
+        for clip in sorted(d for d in os.listdir(img_dir) if os.path.isdir(os.path.join(img_dir, d))):
+            names = sorted(f for f in os.listdir(os.path.join(img_dir, clip)) if f.lower().endswith(".png"))
+            assert len(names) >= 2, f"{clip}: a clip needs at least two frames"
+            imgs = np.stack([np.asarray(Image.open(os.path.join(img_dir, clip, f)).convert("RGB")) for f in names])
+            labs = np.stack([np.asarray(Image.open(os.path.join(seg_dir, clip, f)).convert("L")) for f in names])
+            frames, labels = self._synthesize(syn, torch.from_numpy(imgs)[None].to(self.device),
+                                              torch.from_numpy(labs)[None].to(self.device))
+            frames, labels = frames[0].cpu().numpy(), labels[0].cpu().numpy()
+            vis = palette[np.minimum(labels, len(palette) - 1)]  # (ids past the classes: "none")
+            for sub, arr in (("rgb", frames), ("seg", labels), ("vis_seg", vis)):
+                d = os.path.join(root, sub, clip)
+                os.makedirs(d, exist_ok=True)
+                for k in range(arr.shape[0]):
+                    Image.fromarray(np.ascontiguousarray(arr[k])).save(os.path.join(d, "{:04d}.png".format(k)))
+        return root
+
     def _scalars(self, tag, info):
         path = getattr(self.args, "path", None)
         if path:

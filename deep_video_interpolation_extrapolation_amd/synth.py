@@ -1,0 +1,278 @@
+"""Device-resident video synthesis: uint8 frames and label maps in, uint8 frames and label maps out.
+
+`VideoSynthesizer` runs a trained InterNet / ExtraNet (HRNet coarse model) as a product path:
+
+* every frame lives on the device in two forms: its uint8 RGB / label map (what the caller
+  gave or gets) and, while a later forward still reads it, the fp32 (B, H, W, 8) form the
+  HRNet plan reads -- for an input frame written by `dvie_synth_load`, for a prediction the
+  plan's own raw `rgb` output (unclamped, not re-quantised: what InterTrainer.mini_test
+  feeds back).  Both have the strides of the plan's external output, so any two of them go
+  into the next forward as channel views, in place;
+* the segmentations enter the plan as uint8 label maps (DVIE_EW_LABELS, 1 byte per pixel
+  instead of the 80 of an fp32 one-hot);
+* the plans are forward-only, label-input and arena-allocated (engine.assign_offsets);
+* `dvie_synth_finish` turns a forward's outputs into the uint8 frame and the argmax label;
+* nothing is copied to the host.
+
+Storage is slot-major -- (slots, B, H, W, ...) -- so that one time slot of a chunk of clips is
+one contiguous block: a forward reads slots `left` and `right` of clips b0:b1 and writes slot
+`out` of the same clips, with no gather or scatter.  All (left, right, out) pairs of a level
+form one batch, cut into chunks of at most `max_batch` (VideoSynthesizer.chunks): a chunk that
+stays inside one triple runs on those views; where the clips of a triple do not fill a chunk
+(a single video), a chunk spans several triples, whose frames are gathered into contiguous
+blocks first and whose outputs are scattered back (128 B per pixel and pair, against the
+several KB per pixel the forward itself moves).
+"""
+import ctypes
+
+import torch
+
+from . import _lib as L
+from . import engine as E
+
+_PLAN_FLAGS = ("labels", "alias")
+
+
+def midpoint_schedule(T, levels):
+    """Recursive interpolation of T frames by `levels` doublings: per level the (left, right,
+    out) slot triples, slots numbered 0 .. (T - 1) * 2**levels with the input frames at the
+    multiples of 2**levels.  Level 1 fills the midpoints of the inputs, level j the midpoints
+    of the neighbours at the previous spacing; every other slot is written exactly once."""
+    assert T >= 2 and levels >= 0, (T, levels)
+    last = (T - 1) << levels
+    out = []
+    for j in range(1, levels + 1):
+        s = 1 << (levels - j + 1)
+        out.append([(a, a + s, a + s // 2) for a in range(0, last, s)])
+    return out
+
+
+def synth_load(frames, out):
+    """uint8 RGB frames (..., 3), contiguous -> fp32 `out` (..., ld) (dvie_synth_load)."""
+    L.require_gpu(frames)
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.shape[-1] == 3
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[:-1] == frames.shape[:-1]
+    d = L.SynthLoadDesc()
+    d.frames, d.out, d.npix, d.out_ld = frames.data_ptr(), out.data_ptr(), frames.numel() // 3, out.shape[-1]
+    L.check(L.load().dvie_synth_load(ctypes.byref(d), L.stream_ptr(frames.device)), "synth load")
+    return out
+
+
+def synth_finish(rgb=None, seg=None, frame=None, label=None, n_classes=20):
+    """fp32 `rgb` (..., rgb_ld) -> uint8 `frame` (..., 3) and / or fp32 logits `seg` (..., seg_ld)
+    -> uint8 `label` (...) (dvie_synth_finish; all contiguous, either output may be None)."""
+    d = L.SynthFinishDesc()
+    ref = rgb if frame is not None else seg
+    L.require_gpu(ref)
+    if frame is not None:
+        assert rgb.dtype == torch.float32 and rgb.is_contiguous() and frame.dtype == torch.uint8
+        assert frame.is_contiguous() and frame.shape == rgb.shape[:-1] + (3,), (frame.shape, rgb.shape)
+        d.rgb, d.frame, d.rgb_ld = rgb.data_ptr(), frame.data_ptr(), rgb.shape[-1]
+    if label is not None:
+        assert seg.dtype == torch.float32 and seg.is_contiguous() and label.dtype == torch.uint8
+        assert label.is_contiguous() and label.shape == seg.shape[:-1], (label.shape, seg.shape)
+        d.seg, d.label, d.seg_ld, d.n_classes = seg.data_ptr(), label.data_ptr(), seg.shape[-1], n_classes
+    d.npix = ref.numel() // ref.shape[-1]
+    L.check(L.load().dvie_synth_finish(ctypes.byref(d), L.stream_ptr(ref.device)), "synth finish")
+
+
+class _Captured:
+    """One forward + finish of a fixed (n, H, W) as a hipGraph over static tensors."""
+
+    def __init__(self, syn, n, H, W, dev):
+        f32, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
+        self.xa, self.xb = torch.zeros((n, H, W, 8), **f32), torch.zeros((n, H, W, 8), **f32)
+        self.la, self.lb = torch.zeros((n, H, W), **u8), torch.zeros((n, H, W), **u8)
+        self.rgb = torch.empty((n, H, W, 8), **f32)
+        self.frame, self.label = torch.empty((n, H, W, 3), **u8), torch.empty((n, H, W), **u8)
+        self.plan = syn._plan(n, H, W, dev)
+        syn._logits(n, H, W, dev)  # (allocated here, on the caller's stream, not in the warm-up)
+        self.plan.busy = True  # the graph holds this plan's pointers: nobody else gets it from the pool
+        args = (self.plan, self.xa, self.xb, self.la, self.lb, self.rgb, self.frame, self.label)
+        side = torch.cuda.Stream(dev)  # warm-up on a side stream, as stream capture requires
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            syn._run(*args)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):  # a single-stream chain: the forward list, then finish
+            syn._run(*args)
+
+    def __call__(self, xa, xb, la, lb, rgb, frame, label):
+        for dst, src in ((self.xa, xa), (self.xb, xb), (self.la, la), (self.lb, lb)):
+            dst.copy_(src, non_blocking=True)
+        self.graph.replay()
+        for dst, src in ((rgb, self.rgb), (frame, self.frame), (label, self.label)):
+            dst.copy_(src, non_blocking=True)
+
+
+class VideoSynthesizer:
+    """interpolate / extrapolate uint8 device video with a trained InterNet or ExtraNet.
+
+    net: nets.InterNet or nets.ExtraNet over HRNet (either highres_large setting), one
+    predicted frame per forward (num_pred_once 1, no fix_init_frames / inpaint_mask); it is put
+    in eval mode.  The two-stage, GAN and VAE nets raise ValueError.  max_batch: frame pairs per
+    forward.  graph: replay one captured hipGraph per forward (built per (n, H, W) at first
+    use; call reset() after the net's parameters were moved or replaced)."""
+
+    def __init__(self, net, max_batch=8, graph=False):
+        from .nets.ExtraNet import ExtraNet
+        from .nets.HRNet import HRNet
+        from .nets.InterNet import InterNet
+        if type(net) not in (InterNet, ExtraNet) or type(getattr(net, "coarse_model", None)) is not HRNet:
+            raise ValueError(f"VideoSynthesizer runs InterNet / ExtraNet over HRNet, not {type(net).__name__} "
+                             "(two-stage, GAN and VAE nets are out of scope)")
+        cm = net.coarse_model
+        if cm.npo != 1 or cm.fix_init or cm.inpaint_mask or cm.n_frames != 2:
+            raise ValueError("VideoSynthesizer needs one predicted frame from two (num_pred_once 1, no "
+                             "fix_init_frames / inpaint_mask)")
+        assert max_batch >= 1
+        net.eval()
+        self.net, self.cm, self.max_batch, self.graph = net, cm, int(max_batch), bool(graph)
+        self._seg = {}  # (n, H, W, device) -> logits scratch
+        self._graphs = {}
+
+    def reset(self):
+        """drop the captured graphs and scratch (after net.to(...) or a load that re-allocates)"""
+        for c in self._graphs.values():
+            c.plan.busy = False
+        self._graphs, self._seg = {}, {}
+
+    # ---------------- one forward ----------------
+    def _plan(self, n, H, W, dev):
+        return self.cm._pool.acquire((n, H, W, self.cm.dtype, False, dev, False, False, _PLAN_FLAGS))
+
+    def _logits(self, n, H, W, dev):
+        """the segmentation-logit scratch of an (n, H, W) forward"""
+        key = (n, H, W, dev)
+        if key not in self._seg:
+            self._seg[key] = torch.empty((n, H, W, E.rup(self.cm.seg_out_dim, 8)), dtype=torch.float32, device=dev)
+        return self._seg[key]
+
+    def _run(self, plan, xa, xb, la, lb, rgb, frame, label):
+        """rgb (fp32, raw), frame, label <- net(xa, xb | la, lb); every tensor a contiguous
+        (n, H, W, ...) block (the inputs may be strided over n)."""
+        n, H, W, _ = rgb.shape
+        seg = self._logits(n, H, W, rgb.device)
+        plan.set_input_parts("x", [xa.permute(0, 3, 1, 2)[:, :3], xb.permute(0, 3, 1, 2)[:, :3]])
+        plan.set_input_labels("seg", [la, lb])
+        plan.set_output("rgb", rgb)
+        plan.set_output("segout", seg)
+        plan.run_forward()
+        synth_finish(rgb, seg, frame, label, n_classes=self.cm.n_classes)
+
+    def _pair(self, xa, xb, la, lb, rgb, frame, label):
+        n, H, W, _ = rgb.shape
+        if not self.graph:
+            return self._run(self._plan(n, H, W, rgb.device), xa, xb, la, lb, rgb, frame, label)
+        key = (n, H, W, rgb.device)
+        if key not in self._graphs:
+            self._graphs[key] = _Captured(self, n, H, W, rgb.device)
+        self._graphs[key](xa, xb, la, lb, rgb, frame, label)
+
+    # ---------------- clips ----------------
+    def _check(self, frames, labels):
+        L.require_gpu(frames)
+        if frames.dtype != torch.uint8 or labels.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 \
+                or labels.shape != frames.shape[:4] or labels.device != frames.device:
+            raise ValueError("frames: uint8 (B, T, H, W, 3), labels: uint8 (B, T, H, W), on one device; got "
+                             f"{tuple(frames.shape)} {frames.dtype}, {tuple(labels.shape)} {labels.dtype}")
+        m = 8 if self.cm.highres_large else 4
+        if frames.shape[2] % m or frames.shape[3] % m:
+            raise ValueError(f"H and W must be multiples of {m}, got {tuple(frames.shape[2:4])}")
+
+    def chunks(self, triples, B):
+        """The forwards of one level: its pairs (triple, clip), triples in order and the clips
+        of a triple together, cut into chunks of at most max_batch.  -> [[(left, right, out,
+        b0, b1)]]: a chunk is a list of pieces, one per triple it touches, of clips b0:b1.
+        With B >= max_batch (or one triple) every chunk is one piece."""
+        if B >= self.max_batch or len(triples) == 1:
+            return [[(a, b, o, b0, min(B, b0 + self.max_batch))] for a, b, o in triples
+                    for b0 in range(0, B, self.max_batch)]
+        out, cur, room = [], [], self.max_batch
+        for a, b, o in triples:
+            b0 = 0
+            while b0 < B:
+                n = min(room, B - b0)
+                cur.append((a, b, o, b0, b0 + n))
+                b0, room = b0 + n, room - n
+                if room == 0:
+                    out.append(cur)
+                    cur, room = [], self.max_batch
+        return out + ([cur] if cur else [])
+
+    def _roll(self, frames, labels, n_slots, in_slots, levels, keep):
+        """The slot-major state, the input frames placed and loaded, then the levels (lists of
+        (left, right, out) triples) run in order.  keep(slot): a later forward reads the slot,
+        so its fp32 form is kept (other predictions go through one scratch block)."""
+        B, _, H, W, _ = frames.shape
+        dev = frames.device
+        with torch.no_grad():
+            fr = torch.empty((n_slots, B, H, W, 3), dtype=torch.uint8, device=dev)
+            lb = torch.empty((n_slots, B, H, W), dtype=torch.uint8, device=dev)
+            for t, s in enumerate(in_slots):  # the originals pass through bit for bit
+                fr[s].copy_(frames[:, t])
+                lb[s].copy_(labels[:, t])
+            res = {s: torch.empty((B, H, W, 8), dtype=torch.float32, device=dev) for s in range(n_slots) if keep(s)}
+            tmp = torch.empty((self.max_batch, H, W, 8), dtype=torch.float32, device=dev)
+            tfr = tlb = None
+            for s in in_slots:
+                if s in res:
+                    synth_load(fr[s], res[s])
+            for triples in levels:
+                for chunk in self.chunks(triples, B):
+                    if len(chunk) == 1:  # one triple: its slots are contiguous blocks, used in place
+                        a, b, o, b0, b1 = chunk[0]
+                        rgb = res[o][b0:b1] if o in res else tmp[:b1 - b0]
+                        self._pair(res[a][b0:b1], res[b][b0:b1], lb[a, b0:b1], lb[b, b0:b1], rgb, fr[o, b0:b1],
+                                   lb[o, b0:b1])
+                        continue
+                    # several triples: gather their frames, run one forward, scatter its outputs
+                    n = sum(b1 - b0 for *_, b0, b1 in chunk)
+                    if tfr is None:
+                        tfr = torch.empty((self.max_batch, H, W, 3), dtype=torch.uint8, device=dev)
+                        tlb = torch.empty((self.max_batch, H, W), dtype=torch.uint8, device=dev)
+                    xa = torch.cat([res[a][b0:b1] for a, _, _, b0, b1 in chunk])
+                    xb = torch.cat([res[b][b0:b1] for _, b, _, b0, b1 in chunk])
+                    la = torch.cat([lb[a, b0:b1] for a, _, _, b0, b1 in chunk])
+                    lb2 = torch.cat([lb[b, b0:b1] for _, b, _, b0, b1 in chunk])
+                    self._pair(xa, xb, la, lb2, tmp[:n], tfr[:n], tlb[:n])
+                    k = 0
+                    for _, _, o, b0, b1 in chunk:
+                        m = b1 - b0
+                        fr[o, b0:b1].copy_(tfr[k:k + m])
+                        lb[o, b0:b1].copy_(tlb[k:k + m])
+                        if o in res:
+                            res[o][b0:b1].copy_(tmp[k:k + m])
+                        k += m
+        return fr, lb
+
+    def interpolate(self, frames, labels, levels=1):
+        """frames (B, T, H, W, 3), labels (B, T, H, W), uint8 on the device -> frames
+        (B, (T - 1) * 2**levels + 1, H, W, 3) and labels of the same length (uint8, views of
+        slot-major storage): the inputs unchanged at the multiples of 2**levels, between them
+        the predictions of midpoint_schedule(T, levels).  A predicted frame enters the next
+        level as the network's raw fp32 output and with its argmax label."""
+        self._check(frames, labels)
+        T = frames.shape[1]
+        if T < 2 or levels < 0:
+            raise ValueError("interpolate needs at least two frames and levels >= 0")
+        sched = midpoint_schedule(T, levels)
+        step = 1 << levels
+        n_slots = (T - 1) * step + 1
+        # the last level's predictions (the odd slots) are read by no forward
+        fr, lb = self._roll(frames, labels, n_slots, [t * step for t in range(T)], sched,
+                            keep=lambda s: levels > 0 and s % 2 == 0)
+        return fr.transpose(0, 1), lb.transpose(0, 1)
+
+    def extrapolate(self, frames, labels, steps=1):
+        """frames (B, 2, H, W, 3), labels (B, 2, H, W) -> the `steps` following frames and
+        labels: each step predicts from [previous, last] and appends (the num_pred_once == 1
+        rule of InterTrainer.mini_test)."""
+        self._check(frames, labels)
+        if frames.shape[1] != 2 or steps < 1:
+            raise ValueError("extrapolate needs exactly two frames and steps >= 1")
+        fr, lb = self._roll(frames, labels, 2 + steps, [0, 1], [[(k, k + 1, k + 2)] for k in range(steps)],
+                            keep=lambda s: s <= steps)
+        return fr[2:].transpose(0, 1), lb[2:].transpose(0, 1)

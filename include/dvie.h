@@ -249,6 +249,14 @@ int dvie_pack_blocks(const dvie_pack_desc* d);
  *                 image and for t >= sh0*sw0 (ext_c % 8 == 0).  Lowers a stride-1 conv whose
  *                 input has few channels (the data gradient of HRNet's 3x3 448->3 / 448->20
  *                 heads) to a 1x1 GEMM over K = taps*ext_c instead of taps*64.
+ *  DVIE_EW_LABELS y[n,y,x][k] = (lab[n,y,x] == k) for k < ext_c, 0 for ext_c <= k < c: the
+ *                 one-hot of a uint8 label map, written in the plan dtype.  lab is read
+ *                 through `ext` (reinterpreted as const uint8_t*) with ELEMENT strides sn, sh,
+ *                 sw (sc unused).  A label >= ext_c (Cityscapes' 255 "ignore") gives an
+ *                 all-zero row, as dvie_clip_prep defines it.  A plan input op: it takes no
+ *                 epilogue operand (res / beta / act / dact must be unset).  The values equal
+ *                 what DVIE_EW_NCHW writes from the fp32 one-hot, at 1 B read per pixel
+ *                 instead of 4 * ext_c.
  * then the shared epilogue: v += res; v += y_old (beta); v = act(v); v *= act'(z); y = v.
  * Channels c % 4 == 0; all lds % 4 == 0.
  */
@@ -262,6 +270,7 @@ int dvie_pack_blocks(const dvie_pack_desc* d);
 #define DVIE_EW_TONCHW 7
 #define DVIE_EW_MASK 8
 #define DVIE_EW_IM2COL 9
+#define DVIE_EW_LABELS 10
 
 typedef struct dvie_ew_desc {
   void* y;
@@ -766,9 +775,50 @@ typedef struct dvie_clip_desc {
 
 int dvie_clip_prep(const dvie_clip_desc* d, void* stream);
 
+/*
+ * Device-resident video synthesis (synth.py VideoSynthesizer): the two pointwise ends of an
+ * inference forward, uint8 frames in and uint8 frames / label maps out.
+ *
+ * dvie_synth_load: uint8 RGB frames (npix, 3) -> fp32 (npix, out_ld): channels 0-2 =
+ *   (u8 / 255 - 0.5) / 0.5 (the expression of dvie_clip_prep, bit for bit), channels
+ *   3 .. out_ld-1 = 0.  out_ld = 8 gives the shape and strides of the HRNet plan's external
+ *   `rgb` output, so input frames and predictions feed the next forward as equal-stride
+ *   channel views.  out_ld % 4 == 0, out 16-byte aligned.
+ *
+ * dvie_synth_finish: the fp32 outputs of a forward -> what a viewer wants.
+ *   frame[p][c] = rintf(fminf(fmaxf(rgb[p*rgb_ld + c], -1), 1) * 127.5f + 127.5f), c < 3, with
+ *     the multiply and the add rounded separately (no fma) and round-half-to-even: the
+ *     values of eager (x.clamp(-1, 1) * 127.5 + 127.5).round().
+ *   label[p] = the smallest index among the maxima of seg[p*seg_ld + 0 .. n_classes-1]
+ *     (ascending scan, strict >: torch.argmax / np.argmax on finite inputs).
+ *   Either output may be NULL (rgb / seg is then not read and may be NULL too).  Padding
+ *   channels (rgb 3 .. rgb_ld-1, seg n_classes .. seg_ld-1) never reach a result.  Inputs are
+ *   finite; NaN handling is not part of the contract.  Leading dimensions % 4 == 0, inputs
+ *   16-byte aligned, n_classes <= min(seg_ld, 256).
+ */
+typedef struct dvie_synth_load_desc {
+  const uint8_t* frames;
+  float* out;
+  long long npix;
+  int out_ld, pad0;
+} dvie_synth_load_desc;
+
+typedef struct dvie_synth_finish_desc {
+  const float* rgb;
+  const float* seg;
+  uint8_t* frame;
+  uint8_t* label;
+  long long npix;
+  int rgb_ld, seg_ld, n_classes, pad0;
+} dvie_synth_finish_desc;
+
+int dvie_synth_load(const dvie_synth_load_desc* d, void* stream);
+int dvie_synth_finish(const dvie_synth_finish_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
-/* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op). */
+/* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
+ * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);
