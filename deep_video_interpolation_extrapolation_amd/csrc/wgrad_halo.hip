@@ -77,8 +77,8 @@ __device__ __forceinline__ int xcd_chunk(int b, int nb) {
   return (g < r ? g * (q + 1) : r * (q + 1) + (g - r) * q) + i;
 }
 
-// 8 waves: (co half, ci half, row half); the two row halves accumulate separately and are
-// summed through LDS into one partial slab per split.  NW = 4 (output channels <= 32, the
+// 8 waves: (co half, ci half, row half -- column half in the REUSE form); the two halves
+// accumulate separately and are summed through LDS into one partial slab per split.  NW = 4 (output channels <= 32, the
 // 448 -> 3 / 448 -> 20 heads): no co half -- the second half's waves would only multiply the
 // zero padding of channels 32..63, and without them each wave has its SIMD's MFMA pipe alone.
 //
@@ -91,15 +91,24 @@ __device__ __forceinline__ int xcd_chunk(int b, int nb) {
 // DOB (PIPE form): the bias column sums are compiled in (a launch with p.bws); without them
 // the k-steps carry no v_dot2c (most HRNet convs have no bias: 4 of them per k-step per wave
 // sat beside the MFMAs for nothing)
-template <int TH, int TW, int PR, int TMO, int TMI, int NW = 8, bool PIPE = false, int AB = 0, bool DOB = true>
+// REUSE (PIPE form, 64 x 64 blocks): the two waves of a (co half, ci half) split the tile by
+// COLUMN half instead of row half.  A wave walks the PR rows of one 16-pixel chunk top to bottom
+// and keeps the X fragments of TH consecutive halo rows x TW shifts in registers: the fragment
+// of halo row h and shift tj is tap ti of output row h - ti for every ti, so a row step reads
+// only the next halo row's TW fragments and its G fragment for its TH * TW MFMAs (3x3: 88
+// transposed reads per tile and wave instead of 160).
+template <int TH, int TW, int PR, int TMO, int TMI, int NW = 8, bool PIPE = false, int AB = 0, bool DOB = true,
+          bool REUSE = false>
 __global__ __launch_bounds__(64 * NW) void wgrad_halo_kernel(const dvie_wgrad_desc p, int n_co, int n_ci, int splits,
                                                              int tiles_x, int tiles_y, int n_tiles, int flags) {
   typedef WgCfg<TH, TW, PR, TMO, TMI> C;
   static_assert(PR % 2 == 0, "row halves");
   static_assert(NW == 8 || (NW == 4 && TMO == 1), "4-wave form: one 32-channel co block");
+  static_assert(!REUSE || (PIPE && TMO == 1 && TMI == 1 && TW <= 4), "row-walking form: one fragment per operand");
   __shared__ __attribute__((aligned(1024))) char smem[C::SMEM];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  __builtin_assume(wave >= 0 && wave < NW);  // (folds the piece-count tests of the DMA loops)
   const int merge = flags & 1;
   constexpr int dbg = AB;  // (timing-only ablation bits, above)
   // flags bit 1: static priority for the second-dispatched half of the waves (the arbitration
@@ -264,6 +273,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad_halo_kernel(const dvie_wgrad_de
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
 
+  // (wrow: the row half of the tile, or with REUSE its column half -- disjoint pixels either way)
   const int wco = NW == 8 ? (wave >> 1) & 1 : 0, wci = wave & 1, wrow = NW == 8 ? wave >> 2 : wave >> 1;
   // bias gradient (p.bws): the ci-block-0 workgroups' wci = 0 waves sum the G fragments they
   // already hold for the MFMAs (lane l: co = l % 32 of the fragment, 8 pixels)
@@ -306,7 +316,85 @@ __global__ __launch_bounds__(64 * NW) void wgrad_halo_kernel(const dvie_wgrad_de
     }
     const char* G = smem + gb * C::GSZ;
     const char* X = smem + 2 * C::GSZ;
-    if constexpr (PIPE) {
+    if constexpr (PIPE && REUSE) {
+      // wrow is the COLUMN half here: 16-pixel chunks kx = 2 * wrow + c, c = 0, 1, each walked
+      // over the tile's PR rows.  A step = (chunk c, output row py); the steps of a tile are fully
+      // unrolled, so every fragment index below is a constant (no register rotation).
+      constexpr int NS = 2 * PR;
+      const int cofs = wrow * (32 * 128);  // the wave's first pixel in a G / halo row, in bytes
+      const char* Gc = G + g_off[0] + cofs;
+      const char* Xrow[C::HR];  // ring wrap resolved once per tile
+      {
+        int slot = T.y0 % C::R;
+#pragma unroll
+        for (int j = 0; j < C::HR; ++j) {
+          Xrow[j] = X + slot * (C::XW * 128) + cofs;
+          slot = slot + 1 == C::R ? 0 : slot + 1;
+        }
+      }
+      bf16x8 ga[2][PR], xf[2][C::HR][TW];
+      auto load_x = [&](int c, int h) {  // halo row h of chunk c at its TW shifts (pixel c * 16 + tj)
+#pragma unroll
+        for (int tj = 0; tj < TW; ++tj)
+          xf[c][h][tj] =
+              tr_pair(Xrow[h] + x_off[tj][0] + c * (16 * 128), Xrow[h] + x_off[tj][0] + c * (16 * 128) + 4 * 128);
+      };
+      // what step st needs beyond the window of the step before it: its G fragment and halo row
+      // py + TH - 1; a chunk's first step also the TH - 1 rows above that one
+      auto load = [&](int st) {
+        const int c = st / PR, py = st % PR;
+        if ((dbg & 64) && st >= 2) {  // (ablation: the first two steps' registers stand in)
+          ga[c][py] = ga[0][py & 1];
+#pragma unroll
+          for (int h = py == 0 ? 0 : py + TH - 1; h < py + TH; ++h)
+#pragma unroll
+            for (int tj = 0; tj < TW; ++tj) xf[c][h][tj] = xf[0][h % (TH + 1)][tj];
+          return;
+        }
+        ga[c][py] = tr_pair(Gc + (py * 64 + c * 16) * 128, Gc + (py * 64 + c * 16) * 128 + 4 * 128);
+#pragma unroll
+        for (int h = py == 0 ? 0 : py + TH - 1; h < py + TH; ++h) load_x(c, h);
+      };
+      auto mma = [&](int st) {
+        const int c = st / PR, py = st % PR;
+#pragma unroll
+        for (int ti = 0; ti < TH; ++ti)
+#pragma unroll
+          for (int tj = 0; tj < TW; ++tj) {
+            f32x16& a = acc[ti * TW + tj];
+            const bf16x8 b = xf[c][py + ti][tj];
+            if (dbg & 16)
+              a[0] += __builtin_bit_cast(float, __builtin_bit_cast(i32x4, ga[c][py])[0] ^ __builtin_bit_cast(i32x4, b)[1]);
+            else
+              a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga[c][py], b, a, 0, 0, 0);
+          }
+        if constexpr (DOB) bsum[0] = sum8_bf16(ga[c][py], bsum[0]);
+      };
+      load(0);
+#pragma unroll
+      for (int st = 0; st < NS; ++st) {
+        if (st + 1 < NS) load(st + 1);
+        mma(st);
+        if (st + 1 < NS) {  // the next step's transposed reads spread over this step's MFMAs
+          constexpr int PER_ROW = (2 * (TW + 1) + C::NT - 1) / C::NT;         // a row step's reads
+          constexpr int PER_CHUNK = (2 * (TH * TW + 1) + C::NT - 1) / C::NT;  // a chunk's first window
+          if ((st + 1) % PR == 0) {
+#pragma unroll
+            for (int i = 0; i < C::NT; ++i) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x100, PER_CHUNK, 0);
+            }
+          } else {
+#pragma unroll
+            for (int i = 0; i < C::NT; ++i) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x100, PER_ROW, 0);
+            }
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // the next step's reads stay in this step
+      }
+    } else if constexpr (PIPE) {
       constexpr int NS = (PR / 2) * 4, NB = C::NT * TMI;
       // LDS bases of the halo rows this wave's k-steps read (rows wrow * PR/2 + j of the tile),
       // ring wrap resolved once per tile rather than per k-step and tap
@@ -461,22 +549,38 @@ __global__ __launch_bounds__(64 * NW) void wgrad_halo_kernel(const dvie_wgrad_de
       }
     __syncthreads();
   }
+  // A (tap, 32 x 32 block): the 16 parked values are read together (one LDS wait), then the 16
+  // row stores go out back to back; a block whose 32 output channels all exist carries no
+  // per-row test.  (One read, wait and branch per row made this tail store-issue-bound.)
 #pragma unroll
   for (int t = 0; t < C::NT; ++t) {
     if (merge && (t < TO) != (wrow == 0)) continue;
+    const long long tcol = (long long)(p.ws_taps > 0 ? (p.tmap >> (4 * t)) & 15 : t) * p.c;
 #pragma unroll
     for (int jo = 0; jo < TMO; ++jo)
 #pragma unroll
       for (int ji = 0; ji < TMI; ++ji) {
         const int ci = k0 + wci * 32 * TMI + 32 * ji + r32;
-        if (ci >= p.c) continue;
         const int j = jo * TMI + ji;
+        float v[16];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int co = c0 + wco * 32 * TMO + 32 * jo + 8 * (e >> 2) + 4 * hh + (e & 3);
-          if (co < p.cout && (!(dbg & 32) || acc[t * TMO * TMI + j][e] == 12345.678f))
-            slab[(long long)co * ws_k + (long long)(p.ws_taps > 0 ? (p.tmap >> (4 * t)) & 15 : t) * p.c + ci] =
-                acc[t * TMO * TMI + j][e] + (merge ? X[t * PSZ + (j * 16 + e) * 64] : 0.f);
+        for (int e = 0; e < 16; ++e) v[e] = acc[t * TMO * TMI + j][e];
+        if (merge) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) v[e] += X[t * PSZ + (j * 16 + e) * 64];
+        }
+        if (ci >= p.c) continue;
+        const int cob = c0 + wco * 32 * TMO + 32 * jo;  // the block's first output channel (wave-uniform)
+        float* dst = slab + (long long)(cob + 4 * hh) * ws_k + tcol + ci;
+        if (cob + 32 <= p.cout) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e)
+            if (!(dbg & 32) || v[e] == 12345.678f) dst[(long long)(8 * (e >> 2) + (e & 3)) * ws_k] = v[e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < 16; ++e)
+            if (cob + 4 * hh + 8 * (e >> 2) + (e & 3) < p.cout && (!(dbg & 32) || v[e] == 12345.678f))
+              dst[(long long)(8 * (e >> 2) + (e & 3)) * ws_k] = v[e];
         }
       }
   }
@@ -642,7 +746,8 @@ static bool wgrad_halo_eligible(const dvie_wgrad_desc& p) {
   if (p.dtype != DVIE_BF16) return false;
   if (wg_halo_env_off) return false;
   if (p.sy != 1 || p.sx != 1 || p.ddy != 1 || p.ddx != 1) return false;
-  if (!((p.th == 1 && p.tw == 1) || (p.th == 3 && p.tw == 3) || (p.th <= 2 && p.tw <= 2))) return false;
+  // (the 2 x 2 / 2 x 1 / 1 x 2 tap grids are the stride-2 phase launches' only: ws_taps > 0)
+  if (!((p.th == 1 && p.tw == 1) || (p.th == 3 && p.tw == 3) || (p.ws_taps > 0 && p.th <= 2 && p.tw <= 2))) return false;
   if (p.ws_taps > 0 && (p.ws_taps > 16 || p.th * p.tw > 4)) return false;
   if (p.c % 8 != 0 || p.cout % 8 != 0) return false;
   if (p.g_ld % 8 != 0 || p.x_ld % 8 != 0) return false;
@@ -727,6 +832,13 @@ static bool wg_pipe_on() {
   return !(e && *e == '0');
 }
 
+// DVIE_WG_REUSE (A/B, read per launch): 0 = 3x3 weight gradients on the k-step fragment pipeline
+// (every tap's X fragment read per output row) instead of the row-walking reuse form
+static bool wg_reuse_on() {
+  const char* e = getenv("DVIE_WG_REUSE");
+  return !(e && *e == '0');
+}
+
 // bias partial slabs the halo kernels write to p.bws (0: the launch is not theirs)
 int wgrad_halo_bias_slabs(const dvie_wgrad_desc& p) {
   if (!wgrad_halo_eligible(p)) return 0;
@@ -751,22 +863,38 @@ bool wgrad_halo_launch(const dvie_wgrad_desc& p, hipStream_t s) {
 #define DVIE_WG(TH, PR, TMO, TMI)                                                                                   \
   DVIE_LAUNCH((wgrad_halo_kernel<TH, TH, PR, TMO, TMI>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci, p.splits, \
                      tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio)
+  const bool wg_reuse = wg_reuse_on();
 #ifdef DVIE_TIMING_DBG
   if (p.th == 3 && p.cout > 32 && wg_pipe && wg_dbg()) {
     switch (wg_dbg()) {
-#define DVIE_WG_AB(V)                                                                                             \
-  case V:                                                                                                         \
-    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, V>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci, p.splits, \
-                tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);                                                 \
-    return true;
+#define DVIE_WG_AB(V)                                                                                               \
+  case V: {                                                                                                         \
+    if (wg_reuse)                                                                                                   \
+      DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, V, true, true>), dim3(grid), dim3(512), 0, s, p, n_co, \
+                  n_ci, p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);                                 \
+    else                                                                                                            \
+      DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, V>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,       \
+                  p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);                                       \
+    return true;                                                                                                    \
+  }
       DVIE_WG_AB(8) DVIE_WG_AB(16) DVIE_WG_AB(32) DVIE_WG_AB(64) DVIE_WG_AB(128) DVIE_WG_AB(136) DVIE_WG_AB(80)
-      DVIE_WG_AB(192) DVIE_WG_AB(144)
+      DVIE_WG_AB(192) DVIE_WG_AB(144) DVIE_WG_AB(72)
 #undef DVIE_WG_AB
       default: break;
     }
   }
 #endif
-  if (p.th == 3 && p.cout > 32 && wg_pipe && !p.bws)
+  // 3x3, 64 x 64 blocks: the row-walking fragment-reuse form (DVIE_WG_REUSE=0: the k-step form)
+  if (p.th == 3 && p.cout > 32 && wg_pipe && wg_reuse && !p.bws)
+    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, 0, false, true>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,
+                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
+  else if (p.th == 3 && p.cout > 32 && wg_pipe && wg_reuse)
+    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, 0, true, true>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,
+                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
+  else if (p.th == 3 && p.cout <= 32 && !wg_narrow_env_off && wg_reuse)
+    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 4, true, 0, true, true>), dim3(grid), dim3(256), 0, s, p, n_co, n_ci,
+                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
+  else if (p.th == 3 && p.cout > 32 && wg_pipe && !p.bws)
     DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, 0, false>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,
                 p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
   else if (p.th == 3 && p.cout > 32 && wg_pipe)
