@@ -137,6 +137,14 @@ class SynthFinishDesc(ctypes.Structure):
     ]
 
 
+class SynthBridgeDesc(ctypes.Structure):
+    _fields_ = [
+        ("rgb", vp), ("seg", vp), ("dst", vp), ("npix", i64),
+        ("rgb_ld", i32), ("seg_ld", i32), ("dst_ld", i32), ("dtype", i32),
+        ("n_rgb", i32), ("rgb_w", i32), ("seg_w", i32), ("pad0", i32),
+    ]
+
+
 class BnDesc(ctypes.Structure):
     _fields_ = [
         ("x", vp), ("y", vp), ("g", vp), ("dx", vp), ("gamma", vp), ("beta", vp), ("dgamma", vp), ("dbeta", vp),
@@ -240,7 +248,7 @@ class Op(ctypes.Structure):
 _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, OP_COLSUM: ColsumDesc,
         OP_EW: EwDesc, OP_LOSS: LossDesc, OP_PACK: PackDesc, OP_BN_FWD: BnDesc, OP_HEAD_FWD: HeadDesc,
         OP_ATTN: AttnDesc, OP_HEAD3_BWD: Head3BwdDesc, OP_SEGENC_FWD: SegencDesc, OP_SEGENC_BWD: SegencBwdDesc, OP_WREDUCE_MULTI: WreduceMultiDesc, 100: WarpDesc, 101: SoftmaxDesc, 102: SnLayer, 103: ClipDesc,
-        104: SynthLoadDesc, 105: SynthFinishDesc}
+        104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -251,7 +259,7 @@ EXPORTS = [
     "dvie_reparam_bwd", "dvie_warp_ws_floats", "dvie_clip_prep", "dvie_attn", "dvie_step_inc", "dvie_adamax_dev",
     "dvie_adam_dev", "dvie_mfma_probe", "dvie_launch_probe", "dvie_sum_f32", "dvie_wgrad_bias_slabs", "dvie_head3_bwd",
     "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_pack_blocks", "dvie_trace_kernels", "dvie_traced_kernels",
-    "dvie_synth_load", "dvie_synth_finish",
+    "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge",
 ]
 
 _lib = None
@@ -286,7 +294,8 @@ def load():
         for name in ("dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_reduce", "dvie_colsum", "dvie_ew",
                      "dvie_loss", "dvie_warp_fwd", "dvie_warp_bwd", "dvie_bn_fwd", "dvie_bn_bwd", "dvie_head_fwd",
                      "dvie_head_bwd", "dvie_softmax_fwd", "dvie_softmax_bwd", "dvie_clip_prep", "dvie_attn",
-                     "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish"):
+                     "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
+                     "dvie_synth_bridge"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]

@@ -296,7 +296,8 @@ __global__ __launch_bounds__(256) void ew_kernel(const dvie_ew_desc p, int cq) {
         const int ch = c + k;
         if (ch < p.ext_c) {
           float* d = p.ext + (long long)n * p.sn + (long long)ch * p.sc + (long long)y * p.sh + (long long)x * p.sw;
-          const float t = p.std ? a[k] / p.std[ch] : a[k];  // adjoint of preprocess_norm
+          float t = p.std ? a[k] / p.std[ch] : a[k];  // adjoint of preprocess_norm
+          if (p.align) t = fminf(fmaxf(t, -p.scale), p.scale);  // (inference outputs: the nets' +-10 clamp)
           *d = p.beta ? *d + t : t;
         }
       }

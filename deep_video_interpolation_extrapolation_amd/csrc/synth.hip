@@ -2,7 +2,9 @@
 //   dvie_synth_load    uint8 RGB frames -> the fp32 NHWC form the HRNet plan reads (and writes:
 //                      the shape and strides of its external `rgb` output);
 //   dvie_synth_finish  the plan's fp32 rgb / segmentation-logit outputs -> uint8 frames and
-//                      uint8 label maps (clamp + quantise, argmax).
+//                      uint8 label maps (clamp + quantise, argmax);
+//   dvie_synth_bridge  between two plans of a two-stage forward: an fp32 image and the coarse
+//                      logits -> [clamp(image) | softmax(logits)] in the next plan's input buffer.
 // They replace the eager glue of InterTrainer.mini_test (normalize, argmax, one_hot, cat and
 // the fp32 20-channel one-hot kept per frame).
 //
@@ -103,11 +105,111 @@ __global__ __launch_bounds__(256) void synth_finish_kernel(const dvie_synth_fini
   }
 }
 
+// dvie_synth_bridge: one lane owns one pixel, as in finish (its 16-byte loads walk the pixel's
+// own 12 + 80 bytes of image and logits) and holds the pixel's whole span in registers, so the
+// stores are whole 16-byte vectors of one contiguous run per lane (48 .. 160 B); the runs of a
+// wave are dst_ld apart (contiguous for `in_x`, whose span is the whole pixel).
+// The softmax is softmax_fwd_kernel's (gan.hip), expression for expression: nothing in it is a
+// multiply followed by an add, so there is nothing for -ffp-contract=fast to fuse.
+template <typename T, int NRGB, int RW, int SW>
+__global__ __launch_bounds__(256) void synth_bridge_kernel(const dvie_synth_bridge_desc p) {
+  constexpr int NCLS = 20, SPAN = NRGB * RW + SW, VW = 16 / (int)sizeof(T);
+  static_assert(SPAN % VW == 0, "the span is a whole number of 16-byte vectors");
+  const long long pix = blockIdx.x * 256LL + threadIdx.x;
+  if (pix >= p.npix) return;
+  float o[SPAN];
+#pragma unroll
+  for (int k = 0; k < SPAN; ++k) o[k] = 0.f;  // (the padding channels are written, as zeros)
+  const f32x4 v = *(const f32x4*)(p.rgb + pix * p.rgb_ld);  // v[3] is padding: loaded, never used
+#pragma unroll
+  for (int r = 0; r < NRGB; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[r * RW + c] = fminf(fmaxf(v[c], -1.f), 1.f);
+  const float* s = p.seg + pix * p.seg_ld;
+  float x[NCLS];
+#pragma unroll
+  for (int c0 = 0; c0 < NCLS; c0 += 4) {
+    const f32x4 t = *(const f32x4*)(s + c0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[c0 + k] = t[k];
+  }
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < NCLS; ++k) m = fmaxf(m, x[k]);
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < NCLS; ++k) sum += expf(x[k] - m);
+  const float inv = 1.f / sum;
+#pragma unroll
+  for (int k = 0; k < NCLS; ++k) o[NRGB * RW + k] = expf(x[k] - m) * inv;
+  T* d = (T*)p.dst + pix * p.dst_ld;
+#pragma unroll
+  for (int k = 0; k < SPAN; k += VW) {
+    if constexpr (sizeof(T) == 4) {
+      *(f32x4*)(d + k) = f32x4{o[k], o[k + 1], o[k + 2], o[k + 3]};
+    } else {
+      i32x4 w;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w[j] = (int)((uint32_t)f2bf(o[k + 2 * j]) | ((uint32_t)f2bf(o[k + 2 * j + 1]) << 16));
+      *(i32x4*)(d + k) = w;
+    }
+  }
+}
+
+template <typename T, int NRGB, int RW, int SW>
+static void launch_bridge(const dvie_synth_bridge_desc& d, unsigned blocks, hipStream_t s) {
+  DVIE_LAUNCH((synth_bridge_kernel<T, NRGB, RW, SW>), dim3(blocks), dim3(256), 0, s, d);
+}
+
 }  // namespace dvie
 
 using namespace dvie;
 
 extern "C" {
+
+int dvie_synth_bridge(const dvie_synth_bridge_desc* d, void* stream) {
+  DVIE_CHECK_ARG(d && d->rgb && d->seg && d->dst, "synth_bridge: rgb / seg / dst must not be null");
+  DVIE_CHECK_ARG(d->npix > 0, "synth_bridge: npix must be positive");
+  DVIE_CHECK_ARG(d->dtype == DVIE_F32 || d->dtype == DVIE_BF16, "synth_bridge: dtype=%d", d->dtype);
+  DVIE_CHECK_ARG(d->n_rgb == 1 || d->n_rgb == 2, "synth_bridge: n_rgb=%d must be 1 or 2", d->n_rgb);
+  DVIE_CHECK_ARG(d->rgb_w == 4 || d->rgb_w == 8, "synth_bridge: rgb_w=%d must be 4 or 8", d->rgb_w);
+  DVIE_CHECK_ARG(d->seg_w == 20 || d->seg_w == 24, "synth_bridge: seg_w=%d must be 20 or 24", d->seg_w);
+  const int span = d->n_rgb * d->rgb_w + d->seg_w, es = d->dtype == DVIE_BF16 ? 2 : 4;
+  DVIE_CHECK_ARG(span <= d->dst_ld, "synth_bridge: the span of %d channels does not fit in dst_ld=%d", span, d->dst_ld);
+  DVIE_CHECK_ARG(span * es % 16 == 0 && (long long)d->dst_ld * es % 16 == 0 && (((uintptr_t)d->dst) & 15) == 0,
+                 "synth_bridge: span=%d and dst_ld=%d must be whole 16-byte vectors of the dtype, dst 16-byte aligned",
+                 span, d->dst_ld);
+  DVIE_CHECK_ARG(d->rgb_ld >= 4 && d->rgb_ld % 4 == 0 && d->seg_ld >= 20 && d->seg_ld % 4 == 0 &&
+                     ((((uintptr_t)d->rgb) | ((uintptr_t)d->seg)) & 15) == 0,
+                 "synth_bridge: rgb_ld=%d (>= 4) and seg_ld=%d (>= 20) must be multiples of 4, rgb / seg 16-byte aligned",
+                 d->rgb_ld, d->seg_ld);
+  const long long blocks = (d->npix + 255) / 256;
+  DVIE_CHECK_ARG(blocks < (1LL << 31), "synth_bridge: grid too large");
+  const unsigned nb = (unsigned)blocks;
+  hipStream_t s = (hipStream_t)stream;
+  const int key = (d->n_rgb - 1) * 4 + (d->rgb_w == 8) * 2 + (d->seg_w == 24);
+  if (d->dtype == DVIE_F32) {
+    switch (key) {
+      case 0: launch_bridge<float, 1, 4, 20>(*d, nb, s); break;
+      case 1: launch_bridge<float, 1, 4, 24>(*d, nb, s); break;
+      case 2: launch_bridge<float, 1, 8, 20>(*d, nb, s); break;
+      case 3: launch_bridge<float, 1, 8, 24>(*d, nb, s); break;
+      case 4: launch_bridge<float, 2, 4, 20>(*d, nb, s); break;
+      case 5: launch_bridge<float, 2, 4, 24>(*d, nb, s); break;
+      case 6: launch_bridge<float, 2, 8, 20>(*d, nb, s); break;
+      default: launch_bridge<float, 2, 8, 24>(*d, nb, s); break;
+    }
+  } else {  // (the spans of 28 and 36 channels are no whole bf16 vectors: refused above)
+    switch (key) {
+      case 0: launch_bridge<bf16_t, 1, 4, 20>(*d, nb, s); break;
+      case 3: launch_bridge<bf16_t, 1, 8, 24>(*d, nb, s); break;
+      case 5: launch_bridge<bf16_t, 2, 4, 24>(*d, nb, s); break;
+      default: launch_bridge<bf16_t, 2, 8, 24>(*d, nb, s); break;
+    }
+  }
+  DVIE_RETURN_LAUNCH();
+}
 
 int dvie_synth_load(const dvie_synth_load_desc* d, void* stream) {
   DVIE_CHECK_ARG(d && d->frames && d->out && d->npix > 0, "synth_load: frames / out / npix");

@@ -821,6 +821,7 @@ size_t dvie_abi_sizeof(int which) {
     case 103: return sizeof(dvie_clip_desc);
     case 104: return sizeof(dvie_synth_load_desc);
     case 105: return sizeof(dvie_synth_finish_desc);
+    case 106: return sizeof(dvie_synth_bridge_desc);
     default: return 0;
   }
 }

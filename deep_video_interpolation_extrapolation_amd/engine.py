@@ -388,8 +388,9 @@ class OutNCHWOp(_Op):
     """Sink: copy an internal region to an external NCHW fp32 tensor (outputs whose
     producer carries an activation, e.g. the tanh RGB head of UNet/SepUNet)."""
 
-    def __init__(self, region, key, channels):
+    def __init__(self, region, key, channels, clamp=0.0):
         self.region, self.key, self.channels, self.out, self.act = region, key, channels, None, L.ACT_NONE
+        self.clamp = clamp  # > 0: the values are clamped to [-clamp, clamp] on the way out
 
     def inputs(self):
         return []
@@ -416,6 +417,7 @@ class Graph:
         self.buffers = []
         self.layers = []
         self.outputs = {}
+        self.caller_written = {}  # key -> region the caller writes before run_forward (Graph.caller_input)
         self.n_l1 = 0
 
     # ---------------- builder ----------------
@@ -442,6 +444,15 @@ class Graph:
         """input `key`, frame `frame`, given as a uint8 label map (Plan.set_input_labels)"""
         assert 0 < n_classes <= min(out.c, 256), (n_classes, out.c)
         self._add(LabelInputOp(out, key, frame, n_classes))
+        return out
+
+    def caller_input(self, out, key):
+        """Declare the channel span `out` as written by the caller before every run_forward,
+        with no input op: Plan.input_view(key) hands out the tensor view to write into (the
+        hand-off kernel of a multi-plan inference forward, synth.py).  In an arena the buffer
+        is live from launch 0 (forward_lifetimes)."""
+        assert key not in self.caller_written, key
+        self.caller_written[key] = out
         return out
 
     def conv(self, x, module, out, act=L.ACT_NONE, res=None, cmap=None, trainable=True, name=""):
@@ -521,10 +532,12 @@ class Graph:
         self._add(OutNCHWOp(region, key, channels))
         self.outputs[key] = (region, channels)
 
-    def export_nchw(self, key, region, channels):
+    def export_nchw(self, key, region, channels, clamp=0.0):
         """Copy a region to an external NCHW fp32 tensor with no gradient path (a detached
-        side output, e.g. HRNet's seg-encoder features for the refinement stage)."""
-        self._add(OutNCHWOp(region, key, channels))
+        side output, e.g. HRNet's seg-encoder features for the refinement stage).  The
+        tensor's strides are the caller's (Plan.set_output_nchw), so an NHWC block permuted
+        to NCHW makes it an NHWC fp32 output.  clamp > 0: values clamped to [-clamp, clamp]."""
+        self._add(OutNCHWOp(region, key, channels, clamp))
 
     def pool(self, x, out):
         assert (out.H * 2, out.W * 2, out.c) == (x.H, x.W, x.c)
@@ -635,6 +648,8 @@ def forward_lifetimes(g, nf):
             for r in _op_regions(op):
                 a, b = life.get(id(r.buf), (i, i))
                 life[id(r.buf)] = (min(a, i), max(b, i))
+    for r in getattr(g, "caller_written", {}).values():  # written before launch 0
+        life[id(r.buf)] = (0, life.get(id(r.buf), (0, 0))[1])
     return life
 
 
@@ -1052,6 +1067,8 @@ class Plan:
                 r = op.region
                 o = self.ew_desc(L.EW_TONCHW, nf, r.H, r.W, r.c, 0, 0, [(self.ptr(r), r.buf.C, r.H, r.W)])
                 o.u.ew.ext_c = op.channels
+                if op.clamp:
+                    o.u.ew.align, o.u.ew.scale = 1, float(op.clamp)
                 self.ext_nchw_out = getattr(self, "ext_nchw_out", {})
                 self.ext_nchw_out[op.key] = len(self.fwd)
                 self.fwd.append(o)
@@ -2095,6 +2112,12 @@ class Plan:
             d = self.fwd_arr[idx + self.fwd_off].u.ew
             d.ext = t.data_ptr()
             (d.sn, d.sh, d.sw), d.sc = t.stride(), 0
+
+    def input_view(self, key):
+        """The (n, H, W, c) view, with the buffer's strides, of the caller-written span `key`
+        (Graph.caller_input): the caller fills it before run_forward."""
+        r = self.g.caller_written[key]
+        return r.buf.t[..., r.c0:r.c0 + r.c]
 
     def set_input(self, key, t):
         """Patch the external NCHW fp32 input `t` (any strides) into the forward list."""

@@ -19,6 +19,13 @@ covering all n_scales scales (weights shared across scales, streams and uses):
   target maps, one softmax over the 90 entries, optional 3x5 average pooling
   (stage3_prop), per-map normalised low-resolution weighting, the weighted gather), all
   with their backward in the same plan.  Concats are channel slices of one buffer.
+
+Each net also has an inference lowering (`infer=True`, VideoSynthesizer's two-stage forward):
+forward-only and arena-allocated, its image / softmax input span written by the caller
+(dvie_synth_bridge) instead of input ops, the neighbour segmentations read as uint8 label
+maps, and one output: the finest image, clamped to [-10, 10] as InterRefineNet /
+InterStage3Net.forward clamp it, as an NHWC fp32 (n, H, W, 8) block.  No coarser-scale
+output leaves the plan and nothing computes flow maps.
 """
 import torch
 import torch.nn as nn
@@ -28,6 +35,8 @@ from .. import engine as E
 from ..runtime import FlatParams, PlanFunction, PlanPool, precision_of
 from .conv import Conv2d
 
+OUT_CLAMP = 10.0  # the nets' clamp of a stage's outputs (nets/InterRefineNet.py)
+INFER = "infer"  # last component of an inference plan's pool key
 WH, WW = 5, 9  # attention window (refine_nets.py:250-251)
 NATT = E.rup(2 * WH * WW, 4)  # 90 window weights (+2 pad) per pixel
 
@@ -134,12 +143,15 @@ class SRNRefine(FlatParams, nn.Module):
     _CMAP = ([3, 4, 5] + [-1] * 5 + [0, 1, 2] + [-1] * 5 + list(range(6, 26)) + [-1] * 4 + list(range(26, 40))
              + [-1] * 2)
 
-    def _lower(self, g, H, W, trainable):
+    def _lower(self, g, H, W, trainable, infer=False):
         lw = _Lower(g, trainable, "srn")
         X = g.buffer("in_full", H, W, 56)
-        g.input_nchw(E.R(X, 0, 8), "rgb", ext_c=3)   # the coarsest scale's "previous prediction" is rgb
-        g.input_nchw(E.R(X, 8, 8), "rgb", ext_c=3)
-        g.input_nchw(E.R(X, 16, 24), "seg", ext_c=20)
+        if infer:  # [rgb | rgb | softmax(seg)]: one span, written by dvie_synth_bridge
+            g.caller_input(E.R(X, 0, 40), "bridge")
+        else:
+            g.input_nchw(E.R(X, 0, 8), "rgb", ext_c=3)   # the coarsest scale's "previous prediction" is rgb
+            g.input_nchw(E.R(X, 8, 8), "rgb", ext_c=3)
+            g.input_nchw(E.R(X, 16, 24), "seg", ext_c=20)
         g.input_nchw(E.R(X, 40, 16), "enc", ext_c=14)
         ns = self.n_scales
         pred = hidden = None
@@ -187,14 +199,23 @@ class SRNRefine(FlatParams, nn.Module):
                 o = lw.res(o, self.output_layer[i], f"output_layer.{i}")
             o = lw.conv(o, self.output_layer[3], name="output_layer.3")
             pred = lw.conv(o, self.output_layer[5], act=False, name="output_layer.5")
-            g.output_nchw(f"pred{ns - 1 - si}", pred, 3)
+            if not infer:
+                g.output_nchw(f"pred{ns - 1 - si}", pred, 3)
+            elif si == 0:  # the finest image only, through the compute dtype as the sinks above
+                g.export_nchw("pred", pred, pred.c, clamp=OUT_CLAMP)
         return g
 
     def _build_plan(self, key):
-        n, H, W, dtype, trainable, dev = key
+        n, H, W, dtype, trainable, dev = key[:6]
+        infer = key[6:] == (INFER,)
+        assert not (infer and trainable)
         g = E.Graph(dtype)
-        self._lower(g, H, W, trainable)
-        return g.compile(n, dev, backward=trainable)
+        self._lower(g, H, W, trainable, infer)
+        return g.compile(n, dev, backward=trainable, alias=infer)
+
+    def infer_plan(self, n, H, W, dev):
+        """the inference plan (module docstring) of an (n, H, W) batch"""
+        return self._pool.acquire((n, H, W, self.dtype, False, dev, INFER))
 
     def _on_moved(self):
         self._pool.clear()
@@ -275,13 +296,19 @@ class MSResAttnRefine(FlatParams, nn.Module):
         x = lw.conv(x, seq[0], name=f"{base}.0")
         return lw.conv(x, seq[2], name=f"{base}.2")
 
-    def _lower(self, g, H, W, trainable, prop):
+    def _lower(self, g, H, W, trainable, prop, infer=False):
         lw = _Lower(g, trainable, "att")
         full = {}
         for s_, key, sk, c0 in (("x", "img", "seg", 0), ("f", "nimg", "nseg", 0), ("b", "nimg", "nseg", 1)):
             X = g.buffer(f"in_{s_}", H, W, 24)
-            g.input_nchw(E.R(X, 0, 4), key, ext_c0=3 * c0, ext_c=3)
-            g.input_nchw(E.R(X, 4, 20), sk, ext_c0=20 * c0, ext_c=20)
+            if infer and s_ == "x":  # [img | softmax(seg)]: written by dvie_synth_bridge
+                g.caller_input(E.R(X), "bridge")
+            else:
+                g.input_nchw(E.R(X, 0, 4), key, ext_c0=3 * c0, ext_c=3)
+                if infer:  # the neighbour's uint8 label map, one-hot on the fly
+                    g.input_labels(E.R(X, 4, 20), sk, frame=c0, n_classes=20)
+                else:
+                    g.input_nchw(E.R(X, 4, 20), sk, ext_c0=20 * c0, ext_c=20)
             full[s_] = E.R(X)
         ns = self.n_scales
         probs, self_sims = [], []
@@ -351,17 +378,27 @@ class MSResAttnRefine(FlatParams, nn.Module):
             o = lw.conv(o, self.output_layer[0], name="output_layer.0")
             o = lw.conv(o, self.output_layer[2], name="output_layer.2")
             o = lw.conv(o, self.output_layer[4], act=False, name="output_layer.4")
-            g.output_nchw(f"out{ns - 1 - si}", o, 3)
+            if not infer:
+                g.output_nchw(f"out{ns - 1 - si}", o, 3)
+            elif si == 0:
+                g.export_nchw("out", o, o.c, clamp=OUT_CLAMP)
         g.sims = self_sims
         return g
 
     def _build_plan(self, key):
-        n, H, W, dtype, trainable, prop, dev = key
+        n, H, W, dtype, trainable, prop, dev = key[:7]
+        infer = key[7:] == (INFER,)
+        assert not (infer and trainable)
         g = E.Graph(dtype)
-        self._lower(g, H, W, trainable, prop)
-        plan = g.compile(n, dev, backward=trainable)
+        self._lower(g, H, W, trainable, prop, infer)
+        plan = g.compile(n, dev, backward=trainable, alias=infer)
         plan.sims = g.sims
         return plan
+
+    def infer_plan(self, n, H, W, dev):
+        """the inference plan (module docstring) of an (n, H, W) batch"""
+        prop = bool(getattr(self.args, "stage3_prop", False))
+        return self._pool.acquire((n, H, W, self.dtype, False, prop, dev, INFER))
 
     def _on_moved(self):
         self._pool.clear()

@@ -1,6 +1,7 @@
 """Device-resident video synthesis: uint8 frames and label maps in, uint8 frames and label maps out.
 
-`VideoSynthesizer` runs a trained InterNet / ExtraNet (HRNet coarse model) as a product path:
+`VideoSynthesizer` runs a trained InterNet / ExtraNet (HRNet coarse model), or one of the
+two-stage nets over it (Inter/ExtraRefineNet, Inter/ExtraStage3Net), as a product path:
 
 * every frame lives on the device in two forms: its uint8 RGB / label map (what the caller
   gave or gets) and, while a later forward still reads it, the fp32 (B, H, W, 8) form the
@@ -13,6 +14,16 @@
 * the plans are forward-only, label-input and arena-allocated (engine.assign_offsets);
 * `dvie_synth_finish` turns a forward's outputs into the uint8 frame and the argmax label;
 * nothing is copied to the host.
+
+A two-stage forward is a chain of plans on one stream: the coarse HRNet plan (stem export
+on), `dvie_synth_bridge`, the SRNRefine inference plan and, for the stage-3 nets, a second
+bridge and the MSResAttnRefine inference plan.  A bridge writes [clamp(image, -1, 1) |
+softmax(coarse logits)] straight into the next plan's input buffer (the module forward's
+clamp, channel softmax, casts and NCHW input ops in one launch); stage 3 reads the two input
+frames in place and their label maps.  The predicted image -- returned quantised, fed back
+raw -- is the finest output of the LAST stage with that stage's [-10, 10] clamp (out[2][-1]
+of the refine nets' forward, out[3][-1] of the stage-3 nets'); the label is the argmax of
+the COARSE logits (the refinement stages predict no segmentation).
 
 Storage is slot-major -- (slots, B, H, W, ...) -- so that one time slot of a chunk of clips is
 one contiguous block: a forward reads slots `left` and `right` of clips b0:b1 and writes slot
@@ -58,6 +69,24 @@ def synth_load(frames, out):
     return out
 
 
+def synth_bridge(rgb, seg, dst):
+    """fp32 image `rgb` (..., rgb_ld) and coarse logits `seg` (..., seg_ld), contiguous -> the
+    channel span `dst`, an (n, H, W, c) view of an NHWC fp32 / bf16 buffer (Plan.input_view):
+    c = 40: SRNRefine's [rgb 8 | rgb 8 | softmax 24], c = 24: MSResAttnRefine's [rgb 4 |
+    softmax 20] (dvie_synth_bridge)."""
+    L.require_gpu(rgb)
+    assert rgb.dtype == torch.float32 and rgb.is_contiguous() and seg.dtype == torch.float32 and seg.is_contiguous()
+    assert rgb.shape[:-1] == seg.shape[:-1] == dst.shape[:-1] and dst.dim() == 4, (rgb.shape, seg.shape, dst.shape)
+    n, H, W, c = dst.shape
+    ld = dst.stride(2)
+    assert dst.stride() == (H * W * ld, W * ld, ld, 1) and c in (24, 40), (dst.shape, dst.stride())
+    d = L.SynthBridgeDesc()
+    d.rgb, d.seg, d.dst, d.npix = rgb.data_ptr(), seg.data_ptr(), dst.data_ptr(), n * H * W
+    d.rgb_ld, d.seg_ld, d.dst_ld, d.dtype = rgb.shape[-1], seg.shape[-1], ld, E.dv_dtype(dst.dtype)
+    d.n_rgb, d.rgb_w, d.seg_w = (2, 8, 24) if c == 40 else (1, 4, 20)
+    L.check(L.load().dvie_synth_bridge(ctypes.byref(d), L.stream_ptr(rgb.device)), "synth bridge")
+
+
 def synth_finish(rgb=None, seg=None, frame=None, label=None, n_classes=20):
     """fp32 `rgb` (..., rgb_ld) -> uint8 `frame` (..., 3) and / or fp32 logits `seg` (..., seg_ld)
     -> uint8 `label` (...) (dvie_synth_finish; all contiguous, either output may be None)."""
@@ -77,7 +106,8 @@ def synth_finish(rgb=None, seg=None, frame=None, label=None, n_classes=20):
 
 
 class _Captured:
-    """One forward + finish of a fixed (n, H, W) as a hipGraph over static tensors."""
+    """One forward (every stage of it) + finish of a fixed (n, H, W) as a hipGraph over static
+    tensors."""
 
     def __init__(self, syn, n, H, W, dev):
         f32, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
@@ -85,10 +115,11 @@ class _Captured:
         self.la, self.lb = torch.zeros((n, H, W), **u8), torch.zeros((n, H, W), **u8)
         self.rgb = torch.empty((n, H, W, 8), **f32)
         self.frame, self.label = torch.empty((n, H, W, 3), **u8), torch.empty((n, H, W), **u8)
-        self.plan = syn._plan(n, H, W, dev)
-        syn._logits(n, H, W, dev)  # (allocated here, on the caller's stream, not in the warm-up)
-        self.plan.busy = True  # the graph holds this plan's pointers: nobody else gets it from the pool
-        args = (self.plan, self.xa, self.xb, self.la, self.lb, self.rgb, self.frame, self.label)
+        self.plans = syn._plans(n, H, W, dev)
+        syn._scratch_of(n, H, W, dev)  # (allocated here, on the caller's stream, not in the warm-up)
+        for p in self.plans:
+            p.busy = True  # the graph holds these plans' pointers: nobody else gets them from the pool
+        args = (self.plans, self.xa, self.xb, self.la, self.lb, self.rgb, self.frame, self.label)
         side = torch.cuda.Stream(dev)  # warm-up on a side stream, as stream capture requires
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -108,21 +139,33 @@ class _Captured:
 
 
 class VideoSynthesizer:
-    """interpolate / extrapolate uint8 device video with a trained InterNet or ExtraNet.
+    """interpolate / extrapolate uint8 device video with a trained coarse or two-stage net.
 
-    net: nets.InterNet or nets.ExtraNet over HRNet (either highres_large setting), one
-    predicted frame per forward (num_pred_once 1, no fix_init_frames / inpaint_mask); it is put
-    in eval mode.  The two-stage, GAN and VAE nets raise ValueError.  max_batch: frame pairs per
-    forward.  graph: replay one captured hipGraph per forward (built per (n, H, W) at first
-    use; call reset() after the net's parameters were moved or replaced)."""
+    net: nets.InterNet / ExtraNet, InterRefineNet / ExtraRefineNet (+ SRNRefine) or
+    InterStage3Net / ExtraStage3Net (+ SRNRefine + MSResAttnRefine, any n_scales, stage3_prop
+    on or off) over HRNet (either highres_large setting), one predicted frame per forward
+    (num_pred_once 1, no fix_init_frames / inpaint_mask); it is put in eval mode.  The frame
+    returned and fed back is the last stage's finest image (module docstring); the label comes
+    from the coarse logits.  GAN and VAE nets and a bare HRNet raise ValueError.  max_batch:
+    frame pairs per forward.  graph: replay one captured hipGraph per forward (built per
+    (n, H, W) at first use; call reset() after the net's parameters were moved or replaced)."""
 
     def __init__(self, net, max_batch=8, graph=False):
-        from .nets.ExtraNet import ExtraNet
+        from .nets.ExtraNet import ExtraNet, ExtraRefineNet, ExtraStage3Net
         from .nets.HRNet import HRNet
         from .nets.InterNet import InterNet
-        if type(net) not in (InterNet, ExtraNet) or type(getattr(net, "coarse_model", None)) is not HRNet:
-            raise ValueError(f"VideoSynthesizer runs InterNet / ExtraNet over HRNet, not {type(net).__name__} "
-                             "(two-stage, GAN and VAE nets are out of scope)")
+        from .nets.InterRefineNet import InterRefineNet, InterStage3Net
+        from .nets.refine import MSResAttnRefine, SRNRefine
+        n_stages = {InterNet: 0, ExtraNet: 0, InterRefineNet: 1, ExtraRefineNet: 1, InterStage3Net: 2,
+                    ExtraStage3Net: 2}.get(type(net))
+        if n_stages is None or type(getattr(net, "coarse_model", None)) is not HRNet:
+            raise ValueError(f"VideoSynthesizer runs the coarse and two-stage Inter / Extra nets over HRNet, not "
+                             f"{type(net).__name__} (GAN and VAE nets are out of scope)")
+        if (n_stages >= 1 and type(net.refine_model) is not SRNRefine) or \
+                (n_stages == 2 and type(net.stage3_model) is not MSResAttnRefine):
+            raise ValueError("VideoSynthesizer runs SRNRefine and MSResAttnRefine as the second and third stage")
+        # [SRNRefine][MSResAttnRefine]: the stages after the coarse model
+        self.stages = [getattr(net, name) for name in ("refine_model", "stage3_model")[:n_stages]]
         cm = net.coarse_model
         if cm.npo != 1 or cm.fix_init or cm.inpaint_mask or cm.n_frames != 2:
             raise ValueError("VideoSynthesizer needs one predicted frame from two (num_pred_once 1, no "
@@ -130,42 +173,71 @@ class VideoSynthesizer:
         assert max_batch >= 1
         net.eval()
         self.net, self.cm, self.max_batch, self.graph = net, cm, int(max_batch), bool(graph)
-        self._seg = {}  # (n, H, W, device) -> logits scratch
+        self._scratch = {}  # (n, H, W, device) -> the scratch tensors of a forward
         self._graphs = {}
 
     def reset(self):
         """drop the captured graphs and scratch (after net.to(...) or a load that re-allocates)"""
         for c in self._graphs.values():
-            c.plan.busy = False
-        self._graphs, self._seg = {}, {}
+            for p in c.plans:
+                p.busy = False
+        self._graphs, self._scratch = {}, {}
 
     # ---------------- one forward ----------------
-    def _plan(self, n, H, W, dev):
-        return self.cm._pool.acquire((n, H, W, self.cm.dtype, False, dev, False, False, _PLAN_FLAGS))
+    def _plans(self, n, H, W, dev):
+        """the plans of an (n, H, W) forward: the coarse HRNet plan (exporting its stem features
+        when a refinement stage follows), then the stages' inference plans"""
+        coarse = self.cm._pool.acquire((n, H, W, self.cm.dtype, False, dev, False, bool(self.stages), _PLAN_FLAGS))
+        return [coarse] + [m.infer_plan(n, H, W, dev) for m in self.stages]
 
-    def _logits(self, n, H, W, dev):
-        """the segmentation-logit scratch of an (n, H, W) forward"""
+    def _scratch_of(self, n, H, W, dev):
+        """the scratch of an (n, H, W) forward: the coarse segmentation logits and, with
+        refinement stages, the stem features and the image of every stage but the last"""
         key = (n, H, W, dev)
-        if key not in self._seg:
-            self._seg[key] = torch.empty((n, H, W, E.rup(self.cm.seg_out_dim, 8)), dtype=torch.float32, device=dev)
-        return self._seg[key]
+        if key not in self._scratch:
+            f32 = dict(dtype=torch.float32, device=dev)
+            sc = {"seg": torch.empty((n, H, W, E.rup(self.cm.seg_out_dim, 8)), **f32)}
+            if self.stages:
+                sc["stem"] = torch.empty((n, 7 * self.cm.n_frames, H, W), **f32)
+                sc["img"] = [torch.empty((n, H, W, 8), **f32) for _ in self.stages]
+            self._scratch[key] = sc
+        return self._scratch[key]
 
-    def _run(self, plan, xa, xb, la, lb, rgb, frame, label):
+    def _run(self, plans, xa, xb, la, lb, rgb, frame, label):
         """rgb (fp32, raw), frame, label <- net(xa, xb | la, lb); every tensor a contiguous
         (n, H, W, ...) block (the inputs may be strided over n)."""
         n, H, W, _ = rgb.shape
-        seg = self._logits(n, H, W, rgb.device)
-        plan.set_input_parts("x", [xa.permute(0, 3, 1, 2)[:, :3], xb.permute(0, 3, 1, 2)[:, :3]])
+        sc = self._scratch_of(n, H, W, rgb.device)
+        seg = sc["seg"]
+        imgs = sc.get("img", []) + [rgb]  # the image each plan writes: the last one is the prediction
+        xs = [xa.permute(0, 3, 1, 2)[:, :3], xb.permute(0, 3, 1, 2)[:, :3]]
+        plan = plans[0]
+        plan.set_input_parts("x", xs)
         plan.set_input_labels("seg", [la, lb])
-        plan.set_output("rgb", rgb)
+        plan.set_output("rgb", imgs[0])
         plan.set_output("segout", seg)
+        if self.stages:
+            F, stem = self.cm.n_frames, sc["stem"]
+            plan.set_output_nchw("stem_x", stem[:, :3 * F])
+            for k in range(F):
+                plan.set_output_nchw(f"stem_seg{k}", stem[:, 3 * F + 4 * k:3 * F + 4 * k + 4])
         plan.run_forward()
+        for k, plan in enumerate(plans[1:]):
+            synth_bridge(imgs[k], seg, plan.input_view("bridge"))
+            if k == 0:  # SRNRefine: the stem features [frames, seg_encoder(seg_k)]
+                plan.set_input("enc", sc["stem"])
+                plan.set_output_nchw("pred", imgs[k + 1].permute(0, 3, 1, 2))
+            else:  # MSResAttnRefine: the two input frames and their label maps as neighbours
+                plan.set_input_parts("nimg", xs)
+                plan.set_input_labels("nseg", [la, lb])
+                plan.set_output_nchw("out", imgs[k + 1].permute(0, 3, 1, 2))
+            plan.run_forward()
         synth_finish(rgb, seg, frame, label, n_classes=self.cm.n_classes)
 
     def _pair(self, xa, xb, la, lb, rgb, frame, label):
         n, H, W, _ = rgb.shape
         if not self.graph:
-            return self._run(self._plan(n, H, W, rgb.device), xa, xb, la, lb, rgb, frame, label)
+            return self._run(self._plans(n, H, W, rgb.device), xa, xb, la, lb, rgb, frame, label)
         key = (n, H, W, rgb.device)
         if key not in self._graphs:
             self._graphs[key] = _Captured(self, n, H, W, rgb.device)
@@ -178,7 +250,7 @@ class VideoSynthesizer:
                 or labels.shape != frames.shape[:4] or labels.device != frames.device:
             raise ValueError("frames: uint8 (B, T, H, W, 3), labels: uint8 (B, T, H, W), on one device; got "
                              f"{tuple(frames.shape)} {frames.dtype}, {tuple(labels.shape)} {labels.dtype}")
-        m = 8 if self.cm.highres_large else 4
+        m = max([8 if self.cm.highres_large else 4] + [4 << (s.n_scales - 1) for s in self.stages])
         if frames.shape[2] % m or frames.shape[3] % m:
             raise ValueError(f"H and W must be multiples of {m}, got {tuple(frames.shape[2:4])}")
 

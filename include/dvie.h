@@ -240,7 +240,9 @@ int dvie_pack_blocks(const dvie_pack_desc* d);
  *                 (runners/InterTrainer.py:373-374 of the reference).
  *  DVIE_EW_TONCHW ext (+)= channels [0, ext_c) of src_0 as fp32 with NCHW strides,
  *                 divided by std[c] when std is set (adjoint of the normalisation);
- *                 beta selects accumulate; the NHWC epilogue is not applied.
+ *                 beta selects accumulate; the NHWC epilogue is not applied.  align != 0
+ *                 clamps the value to [-scale, scale] first (fminf(fmaxf(v, -scale), scale):
+ *                 the +-10 clamp of the two-stage nets' outputs, nets/InterRefineNet.py).
  *  DVIE_EW_MASK   y = src_0 * m or src_0 * (1 - m) (ext_c = 0 / 1), m = ext[n, 0, y, x]
  *                 (fp32, NCHW strides): the fg/bg split of nets/SepUNet.py:45-46 (its own
  *                 adjoint with respect to src_0).
@@ -815,10 +817,42 @@ typedef struct dvie_synth_finish_desc {
 int dvie_synth_load(const dvie_synth_load_desc* d, void* stream);
 int dvie_synth_finish(const dvie_synth_finish_desc* d, void* stream);
 
+/*
+ * dvie_synth_bridge: the hand-off between two plans of a two-stage inference forward (coarse
+ * HRNet -> SRNRefine -> MSResAttnRefine).  Per pixel it reads an fp32 image (3 channels at
+ * rgb + p*rgb_ld) and the 20 fp32 coarse segmentation logits (seg + p*seg_ld) and writes one
+ * contiguous channel span of the destination plan's NHWC input buffer, in that plan's dtype
+ * (DVIE_F32, or DVIE_BF16 rounded to nearest even):
+ *
+ *   dst[p*dst_ld + ...] = [ n_rgb x (clamp(rgb) 3, zeros rgb_w - 3) | softmax(seg) 20, zeros seg_w - 20 ]
+ *
+ *   SRNRefine `in_full` [0, 40) of 56: n_rgb 2, rgb_w 8, seg_w 24;
+ *   MSResAttnRefine `in_x` (24):       n_rgb 1, rgb_w 4, seg_w 20.
+ *
+ * clamp(v) = fminf(fmaxf(v, -1), 1).  The softmax is dvie_softmax_fwd's expression: a running
+ * fmaxf over the channels in order, s += expf(x - m) in order, expf(x - m) * (1 / s) -- the
+ * same bits.  Padding channels inside the span are WRITTEN as zeros (an arena buffer holds
+ * whatever ran before); channels outside the span are not touched.
+ * n_rgb in {1, 2}, rgb_w in {4, 8}, seg_w in {20, 24}; the span n_rgb*rgb_w + seg_w <= dst_ld
+ * and a whole number of 16-byte vectors in the destination dtype; dst, rgb, seg 16-byte
+ * aligned, rgb_ld % 4 == 0 (>= 4), seg_ld % 4 == 0 (>= 20), dst_ld * sizeof(element) % 16 == 0.
+ */
+typedef struct dvie_synth_bridge_desc {
+  const float* rgb;
+  const float* seg;
+  void* dst;
+  long long npix;
+  int rgb_ld, seg_ld, dst_ld, dtype;
+  int n_rgb, rgb_w, seg_w, pad0;
+} dvie_synth_bridge_desc;
+
+int dvie_synth_bridge(const dvie_synth_bridge_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
- * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish). */
+ * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
+ * synth_bridge). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

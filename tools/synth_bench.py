@@ -7,9 +7,14 @@
   run alternating in one process after a warm-up, each leg over at least --seconds of work with
   a device synchronisation around it;
 * new frames/s of VideoSynthesizer.interpolate on one video, its pairs batched 8 per forward
-  against one per forward.
+  against one per forward;
+* the two-stage path (--two-stage): arena vs unaliased bytes of the three inference plans,
+  dvie_synth_bridge's GB/s for both destination layouts, and frames/s of an ExtraStage3Net
+  (bf16, stage3_prop) rollout through VideoSynthesizer, eager and graph=True, against the same
+  rollout through the module forward plus torch glue, at 8x256x512 (n_scales 1) and
+  1x1024x2048 (n_scales 3).
 
-    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json]
+    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json] [--two-stage]
 """
 import argparse
 import json
@@ -24,7 +29,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deep_video_interpolation_extrapolation_amd import engine as E  # noqa: E402
 from deep_video_interpolation_extrapolation_amd import nets  # noqa: E402
 from deep_video_interpolation_extrapolation_amd.runners.InterTrainer import InterTrainer  # noqa: E402
-from deep_video_interpolation_extrapolation_amd.synth import VideoSynthesizer, synth_finish, synth_load  # noqa: E402
+from deep_video_interpolation_extrapolation_amd.synth import (VideoSynthesizer, synth_bridge, synth_finish,  # noqa: E402
+                                                              synth_load)
 
 
 def make_net(large=False):
@@ -40,6 +46,39 @@ def arena_numbers():
         _, arena, unaliased = E.arena_layout(g, n)
         out[f"{'large ' if large else ''}{n}x{H}x{W}"] = dict(arena_bytes=arena, unaliased_bytes=unaliased,
                                                               arena_gib=arena / 2 ** 30, unaliased_gib=unaliased / 2 ** 30)
+    return out
+
+
+def make_two_stage(n_scales):
+    a = types.SimpleNamespace(syn_type="extra", highres_large=False, coarse_model="HRNet", precision="bf16",
+                              n_scales=n_scales, stage3_prop=True, refine_model="SRNRefine",
+                              stage3_model="MSResAttnRefine")
+    torch.manual_seed(1024)
+    return nets.ExtraStage3Net(a)
+
+
+TWO_STAGE_SHAPES = ((8, 256, 512, 1), (1, 1024, 2048, 3))  # (n, H, W, n_scales)
+
+
+def two_stage_arena_numbers():
+    """the three inference plans of an ExtraStage3Net forward (bf16, stage3_prop): arena against
+    one buffer per activation (computed, nothing allocated)"""
+    out = {}
+    for n, H, W, ns in TWO_STAGE_SHAPES:
+        net = make_two_stage(ns)
+        cm = net.coarse_model
+        cm._export_stem = True
+        graphs = dict(coarse=cm._lower(E.Graph(torch.bfloat16), H, W, dry=True, labels=True),
+                      srn=net.refine_model._lower(E.Graph(torch.bfloat16), H, W, False, infer=True),
+                      attention=net.stage3_model._lower(E.Graph(torch.bfloat16), H, W, False, True, infer=True))
+        cm._export_stem = False
+        row = {}
+        for k, g in graphs.items():
+            _, arena, unaliased = E.arena_layout(g, n)
+            row[k] = dict(arena_gib=arena / 2 ** 30, unaliased_gib=unaliased / 2 ** 30, ratio=arena / unaliased)
+        row["sum"] = dict(arena_gib=sum(r["arena_gib"] for r in row.values()),
+                          unaliased_gib=sum(r["unaliased_gib"] for r in row.values()))
+        out[f"{n}x{H}x{W} n_scales={ns}"] = row
     return out
 
 
@@ -85,6 +124,80 @@ def kernel_numbers(dev, seconds):
         r_fin, r_load = timed(fin, seconds), timed(load, seconds)
         out[tag] = dict(buffer_sets=sets, finish_us=1e6 / r_fin, finish_gbs=npix * (128 + 4) * r_fin / 1e9,
                         load_us=1e6 / r_load, load_gbs=npix * (3 + 32) * r_load / 1e9)
+    return out
+
+
+def bridge_numbers(dev, seconds):
+    """dvie_synth_bridge into bf16 destinations, both layouts (SRNRefine's 40 of 56 channels,
+    MSResAttnRefine's 24 of 24): us per launch and GB/s of algorithmic bytes (the 32 + 96 B rows of
+    image and logits read, the span written), rotating over enough buffer sets to exceed the
+    256 MiB Infinity Cache"""
+    out = {}
+    for n, H, W in ((8, 256, 512), (1, 1024, 2048)):
+        npix, sets = n * H * W, 12
+        rgb = [torch.rand((n, H, W, 8), device=dev) * 2.4 - 1.2 for _ in range(sets)]
+        seg = [torch.randn((n, H, W, 24), device=dev) for _ in range(sets)]
+        row = {}
+        for tag, span, ld in (("srn", 40, 56), ("attention", 24, 24)):
+            dst = [torch.zeros((n, H, W, ld), dtype=torch.bfloat16, device=dev) for _ in range(sets)]
+            k = [0]
+
+            def run():
+                i = k[0] = (k[0] + 1) % sets
+                synth_bridge(rgb[i], seg[i], dst[i][..., :span])
+
+            r = timed(run, seconds)
+            row[tag] = dict(us=1e6 / r, gbs=npix * (128 + 2 * span) * r / 1e9, buffer_sets=sets)
+            del dst
+        out[f"{n}x{H}x{W}"] = row
+    return out
+
+
+def module_rollout(net, frames, labels, steps):
+    """the baseline: the rollout through the module forward plus torch glue (one-hot, cat, argmax,
+    quantise), everything on the device; the prediction is the last stage's finest image, fed
+    back raw.  The two input frames are normalised by dvie_synth_load, once per rollout (torch
+    divides by a scalar as a multiplication by its reciprocal, which is not the same bits), so
+    that the result can be compared with the synthesiser's"""
+    onehot = lambda lab: torch.nn.functional.one_hot(lab.long(), 20).permute(0, 3, 1, 2).float()  # noqa: E731
+    out_f, out_l = [], []
+    with torch.no_grad():
+        i1, i2 = (synth_load(frames[:, t].contiguous(), torch.empty(frames[:, t].shape[:-1] + (8,), device=frames.device))
+                  .permute(0, 3, 1, 2)[:, :3] for t in range(2))
+        s1, s2 = onehot(labels[:, 0]), onehot(labels[:, 1])
+        for _ in range(steps):
+            res = net(torch.cat([i1, i2], 1), seg=torch.cat([s1, s2], 1))
+            img, lab = res[3][-1], torch.argmax(res[1], dim=1)
+            out_f.append((img.clamp(-1, 1) * 127.5 + 127.5).round().to(torch.uint8).permute(0, 2, 3, 1))
+            out_l.append(lab.to(torch.uint8))
+            i1, i2, s1, s2 = i2, img, s2, onehot(lab)
+    return torch.stack(out_f, 1), torch.stack(out_l, 1)
+
+
+def two_stage_numbers(dev, seconds, steps):
+    out = {}
+    for B, H, W, ns in TWO_STAGE_SHAPES:
+        net = make_two_stage(ns).to(dev).eval()
+        frames = torch.randint(0, 256, (B, 2, H, W, 3), dtype=torch.uint8, device=dev)
+        labels = torch.randint(0, 20, (B, 2, H, W), dtype=torch.uint8, device=dev)
+        eager, graphed = VideoSynthesizer(net, max_batch=B), VideoSynthesizer(net, max_batch=B, graph=True)
+        legs = dict(module=lambda: module_rollout(net, frames, labels, steps),
+                    eager=lambda: eager.extrapolate(frames, labels, steps),
+                    graph=lambda: graphed.extrapolate(frames, labels, steps))
+        for fn in legs.values():  # warm-up: plans, graph capture
+            fn()
+            fn()
+        same = [int((a != b).sum()) for a, b in zip(legs["module"](), legs["eager"]())]  # differing bytes
+        rates = {k: [] for k in legs}
+        for _ in range(3):  # alternating
+            for k, fn in legs.items():
+                rates[k].append(timed(fn, seconds) * B * steps)
+        row = {k: dict(frames_per_s=sorted(v)[1], runs=v) for k, v in rates.items()}
+        row["module_vs_eager_differing_bytes"] = dict(frames=same[0], labels=same[1])
+        out[f"{B}x{H}x{W} n_scales={ns}"] = row
+        graphed.reset()
+        del net, eager, graphed, legs
+        torch.cuda.empty_cache()
     return out
 
 
@@ -139,7 +252,19 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--interpolate-only", action="store_true")
+    ap.add_argument("--two-stage", action="store_true", help="only the two-stage legs")
     a = ap.parse_args()
+    if a.two_stage:
+        res = dict(two_stage_arena=two_stage_arena_numbers())
+        if torch.cuda.is_available():
+            dev = torch.device("cuda:0")
+            res["bridge_bf16"] = bridge_numbers(dev, a.seconds)
+            res["extrapolate_stage3_bf16"] = two_stage_numbers(dev, a.seconds, a.steps)
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     res = dict(arena=arena_numbers())
     if torch.cuda.is_available():
         dev = torch.device("cuda:0")
