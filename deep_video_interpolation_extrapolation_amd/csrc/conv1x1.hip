@@ -749,12 +749,6 @@ struct PreOk {
   static constexpr int v = NS != 1 || MT > 4 ? 0 : V;
 };
 
-// DVIE_1X1_PERSIST=0: one tile per workgroup for multi-K-step layers (A/B runs); read per launch
-static bool persist_env_on() {
-  const char* e = getenv("DVIE_1X1_PERSIST");
-  return !(e && *e == '0');
-}
-
 // DVIE_1X1_DBG (timing only, wrong results; -DDVIE_TIMING_DBG builds only): bit 1 skips the epilogue stores, bit 2 the
 // MFMA loop (operand DMA kept); read per launch
 static int dbg_env() {
@@ -766,22 +760,10 @@ static int dbg_env() {
 #endif
 }
 
-// DVIE_1X1_RING=0: the wide multi-K-step layers on the two-stage kernel (A/B runs); read per launch
-static bool ring_env_on() {
-  const char* e = getenv("DVIE_1X1_RING");
-  return !(e && *e == '0');
-}
-
 // DVIE_1X1_CE=0: the MFMA-layout epilogue stores for the single-K-step wide tiles (A/B runs);
 // read per launch
 static bool ce_env_on() {
   const char* e = getenv("DVIE_1X1_CE");
-  return !(e && *e == '0');
-}
-
-// DVIE_1X1_PRE=0: no epilogue-operand prefetch (A/B runs); read per launch
-static bool pre_env_on() {
-  const char* e = getenv("DVIE_1X1_PRE");
   return !(e && *e == '0');
 }
 
@@ -801,7 +783,7 @@ static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
     const unsigned long long span = ((unsigned long long)p.n * p.yh * p.yw - 1) * (unsigned long long)p.y_ld * 2ull +
                                     (unsigned long long)p.cout * 2ull;
     const unsigned long long xspan = ((unsigned long long)npix - 1) * (unsigned long long)p.x_ld * 2ull + (unsigned long long)p.c * 2ull;
-    if (ring_env_on() && p.c > KC && n_tiles > 256 && !p.res && !p.beta && !p.dact && span < 0xFFFFFF00ull &&
+    if (p.c > KC && n_tiles > 256 && !p.res && !p.beta && !p.dact && span < 0xFFFFFF00ull &&
         xspan < 0xFFFFFF00ull && p.ih == p.oh && p.iw == p.ow &&
         (p.act == DVIE_ACT_NONE || (p.act == DVIE_ACT_LRELU && p.alpha >= 0.f && p.alpha <= 1.f))) {
 #ifdef DVIE_TIMING_DBG
@@ -829,7 +811,7 @@ static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
     // wide tiles of the heads measured no gain, 896->448 +3%: they keep one tile per workgroup)
     const int per_cu = 163840 / C::SMEM;
     const int G = 256 * (per_cu > 2 ? 2 : per_cu);
-    if (persist_env_on() && p.c > KC && n_tiles > G) {
+    if (p.c > KC && n_tiles > G) {
       DVIE_LAUNCH((conv1x1_persist_kernel<TMC, NS, KC, NWP, MI, NWC>), dim3(G), dim3(64 * NW), 0, s, p, n_ct,
                          n_tiles);
       return;
@@ -840,33 +822,33 @@ static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
   const bool ident = p.osy == 1 && p.osx == 1 && p.ory == 0 && p.orx == 0 && p.yh == p.oh && p.yw == p.ow;
   int pre = 0;
   if constexpr (NS == 1) {
-    if (ident && p.c <= KC && pre_env_on()) {
+    if (ident && p.c <= KC) {
       pre = MI * TMC > 4 ? 0 : (p.res ? 1 : 0) | (p.beta ? 2 : 0) | (p.dact ? 4 : 0);
     }
   }
   if constexpr (NS == 1 && MI == 1 && 2 * TMC == 8) {
     if (ident && ce_env_on() && p.cout % C::BC == 0) {
       switch (pre) {
-#define DVIE_1X1_CE_CASE(V)                                                                                          \
+#define DVIE_CE_CASE(V)                                                                                              \
   case V:                                                                                                            \
     DVIE_LAUNCH((conv1x1_kernel<TMC, NS, KC, NWP, MI, NWC, false, PreOk<V, NS, MI * TMC>::v, true>), dim3(n_tiles), \
                        dim3(64 * NW), 0, s, p, n_ct, n_tiles, 0);                                                     \
     return;
-        DVIE_1X1_CE_CASE(0) DVIE_1X1_CE_CASE(1) DVIE_1X1_CE_CASE(2) DVIE_1X1_CE_CASE(3) DVIE_1X1_CE_CASE(4)
-        DVIE_1X1_CE_CASE(5) DVIE_1X1_CE_CASE(6) DVIE_1X1_CE_CASE(7)
-#undef DVIE_1X1_CE_CASE
+        DVIE_CE_CASE(0) DVIE_CE_CASE(1) DVIE_CE_CASE(2) DVIE_CE_CASE(3) DVIE_CE_CASE(4)
+        DVIE_CE_CASE(5) DVIE_CE_CASE(6) DVIE_CE_CASE(7)
+#undef DVIE_CE_CASE
       }
     }
   }
   switch (pre) {
-#define DVIE_1X1_PRE_CASE(V)                                                                                      \
+#define DVIE_PRE_CASE(V)                                                                                          \
   case V:                                                                                                        \
     DVIE_LAUNCH((conv1x1_kernel<TMC, NS, KC, NWP, MI, NWC, false, PreOk<V, NS, MI * TMC>::v>), dim3(n_tiles), \
                        dim3(64 * NW), 0, s, p, n_ct, n_tiles, dbg_env());                                                   \
     break;
-    DVIE_1X1_PRE_CASE(1) DVIE_1X1_PRE_CASE(2) DVIE_1X1_PRE_CASE(3) DVIE_1X1_PRE_CASE(4) DVIE_1X1_PRE_CASE(5)
-    DVIE_1X1_PRE_CASE(6) DVIE_1X1_PRE_CASE(7)
-#undef DVIE_1X1_PRE_CASE
+    DVIE_PRE_CASE(1) DVIE_PRE_CASE(2) DVIE_PRE_CASE(3) DVIE_PRE_CASE(4) DVIE_PRE_CASE(5)
+    DVIE_PRE_CASE(6) DVIE_PRE_CASE(7)
+#undef DVIE_PRE_CASE
     default:
       DVIE_LAUNCH((conv1x1_kernel<TMC, NS, KC, NWP, MI, NWC, false>), dim3(n_tiles), dim3(64 * NW), 0, s, p, n_ct, n_tiles, dbg_env());
   }
@@ -879,44 +861,27 @@ bool conv1x1_launch(const dvie_conv_desc& p, hipStream_t s) {
   if (p.osy < 1 || p.osx < 1 || p.ory < 0 || p.orx < 0) return false;
   if (p.c % 64 != 0 && p.c > 64) return false;
   if ((long long)p.n * p.oh * p.ow >= (1LL << 31)) return false;
-  const char* e = getenv("DVIE_CONV_CFG");
-  int cfg = e && *e ? atoi(e) : -3;
-  if (cfg >= 0 && cfg < 100) return false;  // tuning override forces the halo / per-tap kernels
   const int cout = p.cout;
   const bool one = p.c <= 64;  // a single K-step: one stage, several workgroups per CU
-
-  // wide layers: 2-D wave grid (116; 448->448 heads 724 -> 662 us, 64->256 166 -> 155 us
-  // at 8x256x512, tools/conv_tune.py)
-  // (DVIE_CONV1X1_WIDE overrides the wide-layer choice alone, for A/B runs of the whole step)
-  static const int wide = getenv("DVIE_CONV1X1_WIDE") && *getenv("DVIE_CONV1X1_WIDE") ? atoi(getenv("DVIE_CONV1X1_WIDE")) : 116;
-  // single K-step, 65-128 output channels: two 64-channel column tiles with every epilogue
-  // operand prefetched beat one 128-channel tile (8x128x256 64->128: 33 vs 35 us residual,
-  // 48 vs 56 us accumulate + activation input, tools/conv_epi_micro.py)
-  // single K-step wide layers (layer1's 64->256 forward, the 256-channel data gradients of its
-  // 256->64 convs): 128-channel wave tiles of 4 accumulators with every epilogue operand
-  // prefetched (101) beat the 2-D wave grid's 8 (116): 213.5 -> 214.7 frames/s, 5 of 6 same-box
-  // pairs (profiles/r03wide1/); DVIE_CONV1X1_WIDE1 overrides it (A/B runs)
-  static const int wide1 = getenv("DVIE_CONV1X1_WIDE1") && *getenv("DVIE_CONV1X1_WIDE1") ? atoi(getenv("DVIE_CONV1X1_WIDE1")) : 101;
-  if (cfg < 0) cfg = cout <= 64 ? 100 : cout <= 128 ? (one ? 100 : 101) : one ? wide1 : wide;
-  switch (cfg) {
-    case 100: one ? launch_1x1<2, 1>(p, s) : launch_1x1<2, 3>(p, s); break;
-    case 101: one ? launch_1x1<4, 1>(p, s) : launch_1x1<4, 3>(p, s); break;
-    case 102: one ? launch_1x1<7, 1>(p, s) : launch_1x1<7, 2>(p, s); break;
-    case 103: one ? launch_1x1<8, 1>(p, s) : launch_1x1<8, 2>(p, s); break;
-    case 104: one ? launch_1x1<4, 1>(p, s) : launch_1x1<4, 2>(p, s); break;
-    // 32-channel K-steps: deeper pipelines in the same LDS (measured: no gain, the kernel is
-    // not load-latency bound)
-    case 105: one ? launch_1x1<7, 1>(p, s) : launch_1x1<7, 4, 32>(p, s); break;
-    case 106: one ? launch_1x1<7, 1>(p, s) : launch_1x1<7, 5, 32>(p, s); break;
-    // 4-wave workgroups (128-pixel tiles, two workgroups per CU)
-    case 110: one ? launch_1x1<7, 1, 64, 4>(p, s) : launch_1x1<7, 2, 32, 4>(p, s); break;
-    // 2-D wave grids: 64-pixel x 128-channel wave tiles (6 fragments per 8 MFMAs)
-    case 116: one ? launch_1x1<4, 1, 64, 4, 2, 2>(p, s) : launch_1x1<4, 2, 64, 4, 2, 2>(p, s); break;
-    case 118: one ? launch_1x1<2, 1, 64, 4, 2, 2>(p, s) : launch_1x1<2, 3, 64, 4, 2, 2>(p, s); break;
-    case 119: one ? launch_1x1<4, 1, 64, 4, 2, 2>(p, s) : launch_1x1<4, 4, 32, 4, 2, 2>(p, s); break;
-    case 120: one ? launch_1x1<4, 1, 64, 4, 2, 2>(p, s) : launch_1x1<4, 5, 32, 4, 2, 2>(p, s); break;
-    default: return false;
-  }
+  // Tile shapes <channel 32-blocks per wave, stages[, K-step, pixel waves, pixel blocks per wave,
+  // channel waves]> (the measurements are in DESIGN.md):
+  // * <= 64 output channels, and 65-128 from a single K-step: 64-channel column tiles (two of
+  //   them with every epilogue operand prefetched beat one 128-channel tile, 8x128x256 64->128:
+  //   33 vs 35 us residual, 48 vs 56 us accumulate + activation input, tools/conv_epi_micro.py)
+  // * 65-128 output channels from several K-steps, and wider layers from a single K-step
+  //   (layer1's 64->256 forward, the 256-channel data gradients of its 256->64 convs):
+  //   128-channel wave tiles of 4 accumulators, every epilogue operand prefetched
+  //   (profiles/r03wide1/)
+  // * wider layers with several K-steps: the 2-D wave grid of 64-pixel x 128-channel wave tiles
+  //   (448->448 heads 724 -> 662 us at 8x256x512)
+  if (cout <= 64 || (cout <= 128 && one))
+    one ? launch_1x1<2, 1>(p, s) : launch_1x1<2, 3>(p, s);
+  else if (cout <= 128)
+    launch_1x1<4, 3>(p, s);
+  else if (one)
+    launch_1x1<4, 1>(p, s);
+  else
+    launch_1x1<4, 2, 64, 4, 2, 2>(p, s);
   return true;
 }
 

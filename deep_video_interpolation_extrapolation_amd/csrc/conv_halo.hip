@@ -119,7 +119,7 @@ __global__ __launch_bounds__(WC* WP * 64) void conv_halo_kernel(const dvie_conv_
   const int wc = wave / WP, wp = wave % WP;
   const int r32 = lane & 31, hh = lane >> 5;
   const int nchunks = (p.c + 63) >> 6;  // c < 64: one zero-padded chunk
-  // epi_pre bit 1: static priority for the second-dispatched half of the waves (DVIE_SETPRIO)
+  // epi_pre bit 1: static priority for the second-dispatched half of the waves (off: HALO_SETPRIO)
   if ((epi_pre & 2) && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
   const unsigned OOB = 0xFFFFFFF0u;
 
@@ -445,17 +445,18 @@ __global__ __launch_bounds__(WC* WP * 64) void conv_halo_kernel(const dvie_conv_
   }
 }
 
-// DVIE_EPI_PREFETCH=0: epilogue operands loaded in the epilogue (A/B runs)
-static const bool epi_prefetch_on = !(getenv("DVIE_EPI_PREFETCH") && *getenv("DVIE_EPI_PREFETCH") == '0');
-static const int halo_setprio = getenv("DVIE_SETPRIO") && *getenv("DVIE_SETPRIO") == '1' ? 2 : 0;
-// DVIE_HALO_WAIT=0: every step waits for all loads issued before it (A/B runs); read per launch
-static int halo_wait_flag() {
-  const char* e = getenv("DVIE_HALO_WAIT");
+// conv_halo_kernel's runtime `epi_pre` bits: the settled side of each retired A/B switch, passed
+// as constants (the kernel still branches on them; folding them in changes its ISA and is a
+// separate, measured change -- DESIGN.md)
+constexpr int HALO_EPI_PREFETCH = 1;  // epilogue operands prefetched during the last K-step (bf16 output)
+constexpr int HALO_SETPRIO = 0;       // (2 = raised priority for the upper waves: measured neutral, off)
+constexpr int HALO_WAIT = 4;          // counted waits: a step waits only for the loads it consumes
+static int halo_dbg_flags() {
 #ifdef DVIE_TIMING_DBG
   const char* d = getenv("DVIE_HALO_DBG");  // timing experiments only: 8 = no weight, 16 = no halo streaming
-  return (e && *e == '0' ? 0 : 4) | (d && *d ? (atoi(d) & 24) : 0);
+  return d && *d ? (atoi(d) & 24) : 0;
 #else
-  return e && *e == '0' ? 0 : 4;
+  return 0;
 #endif
 }
 
@@ -476,13 +477,13 @@ static bool try_halo(const dvie_conv_desc& p, hipStream_t s) {
     const int grid = persistent ? cap : n_tiles;
     if constexpr (PH4)
       DVIE_LAUNCH((conv_halo_kernel<TM, WC, WP, TH, TW, false, true>), dim3(grid), dim3(C::NTH), 0, s, p, n_ct,
-                  n_tiles, tiles_x, tiles_y, persistent, (epi_prefetch_on ? 1 : 0) | halo_setprio | halo_wait_flag());
+                  n_tiles, tiles_x, tiles_y, persistent, HALO_EPI_PREFETCH | HALO_SETPRIO | HALO_WAIT | halo_dbg_flags());
     else if (p.out_f32)
       DVIE_LAUNCH((conv_halo_kernel<TM, WC, WP, TH, TW, true>), dim3(grid), dim3(C::NTH), 0, s, p, n_ct,
-                         n_tiles, tiles_x, tiles_y, persistent, halo_setprio | halo_wait_flag());
+                         n_tiles, tiles_x, tiles_y, persistent, HALO_SETPRIO | HALO_WAIT | halo_dbg_flags());
     else
       DVIE_LAUNCH((conv_halo_kernel<TM, WC, WP, TH, TW, false>), dim3(grid), dim3(C::NTH), 0, s, p, n_ct,
-                         n_tiles, tiles_x, tiles_y, persistent, (epi_prefetch_on ? 1 : 0) | halo_setprio | halo_wait_flag());
+                         n_tiles, tiles_x, tiles_y, persistent, HALO_EPI_PREFETCH | HALO_SETPRIO | HALO_WAIT | halo_dbg_flags());
     return true;
   }
 }
@@ -492,14 +493,10 @@ static bool try_halo(const dvie_conv_desc& p, hipStream_t s) {
 template <int TH, int TW>
 static bool launch_cfg(int cfg, const dvie_conv_desc& p, hipStream_t s) {
   switch (cfg) {
-    case 0: return try_halo<2, 1, 4, TH, TW>(p, s);  // 64 co x 4 rows, 4 waves
-    case 1: return try_halo<2, 2, 2, TH, TW>(p, s);  // 128 co x 2 rows, 4 waves
     case 2: return try_halo<1, 1, 4, TH, TW>(p, s);  // 32 co x 4 rows, 4 waves
     case 3: return try_halo<1, 2, 4, TH, TW>(p, s);  // 64 co x 4 rows, 8 waves
     case 4: return try_halo<2, 2, 4, TH, TW>(p, s);  // 128 co x 4 rows, 8 waves
     case 5: return try_halo<1, 4, 2, TH, TW>(p, s);  // 128 co x 2 rows, 8 waves
-    case 6: return try_halo<1, 1, 8, TH, TW>(p, s);  // 32 co x 8 rows, 8 waves
-    case 7: return try_halo<2, 1, 8, TH, TW>(p, s);  // 64 co x 8 rows, 8 waves
   }
   return false;
 }
@@ -507,13 +504,6 @@ static bool launch_cfg(int cfg, const dvie_conv_desc& p, hipStream_t s) {
 template <int TH, int TW>
 static bool launch_cfg2(int cfg, const dvie_conv_desc& p, hipStream_t s) {
   return cfg == 3 ? try_halo<1, 2, 4, TH, TW>(p, s) : try_halo<2, 2, 4, TH, TW>(p, s);
-}
-
-static int env_cfg() {
-  // tuning override (read per launch so a tuner can sweep it in one process):
-  // -1 = per-tap kernel (conv_fwd.hip), 0..4 = halo configuration, unset = automatic
-  const char* e = getenv("DVIE_CONV_CFG");
-  return e && *e ? atoi(e) : -3;
 }
 
 // Epilogue of one 32-channel x 32-pixel accumulator block (v_mfma_f32_32x32x16 layout):
@@ -692,16 +682,11 @@ static void launch_ws_rows(const dvie_conv_desc& p, hipStream_t s) {
                        tiles_y, persistent);
 }
 
-// tuning knob (read once): DVIE_WS_ROWS = 2 (default: two workgroups per CU, +1.3% step
-// same-box A/B 192.8-193.1 vs 190.5 frames/s, profiles/r02_ab/ab_wsrows.txt) or 4
-static const int ws_rows = getenv("DVIE_WS_ROWS") && atoi(getenv("DVIE_WS_ROWS")) == 4 ? 4 : 2;
-
+// two-row tiles, two workgroups per CU: +1.3% step over four-row tiles (same-box A/B
+// 192.8-193.1 vs 190.5 frames/s, profiles/r02_ab/ab_wsrows.txt)
 template <int KS>
 static void launch_ws(const dvie_conv_desc& p, hipStream_t s) {
-  if (ws_rows == 2)
-    launch_ws_rows<KS, 2>(p, s);
-  else
-    launch_ws_rows<KS, 4>(p, s);
+  launch_ws_rows<KS, 2>(p, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1578,30 +1563,15 @@ static bool conv_h8_launch(const dvie_conv_desc& p, hipStream_t s) {
   if (nt < 224 || nt >= (1LL << 30)) return false;  // fewer tiles than CUs: the 4-row kernel
   const int n_tiles = (int)nt;
   switch ((p.res ? 1 : 0) | (p.beta ? 2 : 0) | (p.dact ? 4 : 0)) {
-    case 0: launch_h8<0>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
-    case 1: launch_h8<1>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
-    case 2: launch_h8<2>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
-    case 3: launch_h8<3>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
-    case 4: launch_h8<4>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
-    case 5: launch_h8<5>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
-    case 6: launch_h8<6>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
-    default: launch_h8<7>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
+#define DVIE_H8(EPI) \
+  case EPI: launch_h8<EPI>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
+    DVIE_H8(0) DVIE_H8(1) DVIE_H8(2) DVIE_H8(3) DVIE_H8(4) DVIE_H8(5) DVIE_H8(6) DVIE_H8(7)
+#undef DVIE_H8
   }
   return true;
 }
 
-// DVIE_CONV_NK=0: narrow-input 3x3 convs on the chunked kernels (A/B runs)
-static const bool nk_env_off = getenv("DVIE_CONV_NK") && *getenv("DVIE_CONV_NK") == '0';
-
 bool conv_narrow_launch(const dvie_conv_desc& p, hipStream_t s);  // conv_narrow.hip
-
-// DVIE_PH4_CFG: tile configuration of the one-launch stride-2 data gradient (3 = 64 channels
-// x 4 rows, 4 = 128 x 4; A/B runs)
-static int ph4_cfg(const dvie_conv_desc& p) {
-  const char* e = getenv("DVIE_PH4_CFG");
-  if (e && *e) return atoi(e);
-  return p.cout % 128 == 0 ? 4 : 3;
-}
 
 // The stride-2 data gradient's four phases in one launch (dvie_conv_desc.phc > 0); false:
 // the descriptor does not meet the kernel's conditions (the caller reports it).
@@ -1614,7 +1584,8 @@ bool conv_halo_ph4_launch(const dvie_conv_desc& p, hipStream_t s) {
   const unsigned long long pix = (unsigned long long)p.n * p.ih * p.iw;
   if (pix >= (1ull << 31) || ((pix - 1) * (unsigned long long)p.x_ld + (unsigned long long)p.c) * 2ull >= 0xFFFFFF00ull)
     return false;
-  return ph4_cfg(p) == 3 ? try_halo<1, 2, 4, 2, 2, true>(p, s) : try_halo<2, 2, 4, 2, 2, true>(p, s);
+  // 128 channels x 4 rows when the channels divide, else 64 x 4
+  return p.cout % 128 != 0 ? try_halo<1, 2, 4, 2, 2, true>(p, s) : try_halo<2, 2, 4, 2, 2, true>(p, s);
 }
 
 // Returns true when the halo kernel took the launch.
@@ -1631,9 +1602,7 @@ bool conv_halo_launch(const dvie_conv_desc& p, hipStream_t s) {
   // 32-bit halo offsets: the input's byte span must fit (dvie_conv2d_fwd rejects larger
   // inputs for every kernel; kept here so the halo path never relies on the caller)
   if (((pix - 1) * (unsigned long long)p.x_ld + (unsigned long long)p.c) * 2ull >= 0xFFFFFF00ull) return false;
-  int cfg = env_cfg();
-  if (cfg == -1) return false;
-  if (t3 && !nk_env_off && cfg == -3 && p.c % 8 == 0 && p.c <= 24 && p.kpad >= 9 * p.c) {
+  if (t3 && p.c % 8 == 0 && p.c <= 24 && p.kpad >= 9 * p.c) {
     switch (p.c / 8) {
       case 1: launch_nk<1>(p, s); break;
       case 2: launch_nk<2>(p, s); break;
@@ -1641,7 +1610,7 @@ bool conv_halo_launch(const dvie_conv_desc& p, hipStream_t s) {
     }
     return true;
   }
-  if (t3 && p.c <= 64 && p.cout <= 64 && (cfg == -3 || cfg == 8) && (long long)p.n * p.oh * p.ow >= 65536) {
+  if (t3 && p.c <= 64 && p.cout <= 64 && (long long)p.n * p.oh * p.ow >= 65536) {
     // single input chunk, one 64-channel output tile: weights stay in VGPRs
     switch ((p.c + 15) / 16) {
       case 1: if (!launch_strip<1>(p, s)) launch_ws<1>(p, s); break;
@@ -1653,20 +1622,19 @@ bool conv_halo_launch(const dvie_conv_desc& p, hipStream_t s) {
   }
   // <= 32 output channels from > 64 input channels (the HRNet heads): one step per 32-channel
   // chunk with all 9 taps (conv_narrow.hip)
-  if (t3 && cfg == -3 && conv_narrow_launch(p, s)) return true;
-  if (t3 && cfg == -3 && conv_h8_launch(p, s)) return true;
-  if (cfg < 0) {  // measured on MI355X (tools/conv_tune.py): see DESIGN.md
-    if (p.cout <= 32)
-      cfg = 2;
-    else if (t1)  // 1x1: wide weight tiles amortise the per-chunk pixel tile
-      cfg = p.cout <= 64 ? 3 : (p.c <= 64 ? 5 : 4);
-    else
-      cfg = (p.cout <= 64 || p.cout % 128 != 0) ? 3 : 4;
-    // fewer 4-row tiles than CUs (VGG19's deep data gradients on 8 frames, 512 -> 512 at
-    // 16 x 32 and 512 -> 256 at 32 x 64): 2-row tiles of the same 128 channels fill the chip,
-    // 52.9 -> 40.9 and 55.5 -> 43.5 us (profiles/r06/vgg_tune.txt)
-    if (t3 && cfg == 4 && (long long)(p.cout / 128) * ((p.ow + 63) / 64) * ((p.oh + 3) / 4) * p.n < 256) cfg = 5;
-  }
+  if (t3 && conv_narrow_launch(p, s)) return true;
+  if (t3 && conv_h8_launch(p, s)) return true;
+  int cfg;  // measured on MI355X: see DESIGN.md
+  if (p.cout <= 32)
+    cfg = 2;
+  else if (t1)  // 1x1: wide weight tiles amortise the per-chunk pixel tile
+    cfg = p.cout <= 64 ? 3 : (p.c <= 64 ? 5 : 4);
+  else
+    cfg = (p.cout <= 64 || p.cout % 128 != 0) ? 3 : 4;
+  // fewer 4-row tiles than CUs (VGG19's deep data gradients on 8 frames, 512 -> 512 at
+  // 16 x 32 and 512 -> 256 at 32 x 64): 2-row tiles of the same 128 channels fill the chip,
+  // 52.9 -> 40.9 and 55.5 -> 43.5 us (profiles/r06/vgg_tune.txt)
+  if (t3 && cfg == 4 && (long long)(p.cout / 128) * ((p.ow + 63) / 64) * ((p.oh + 3) / 4) * p.n < 256) cfg = 5;
   if (t3) return launch_cfg<3, 3>(cfg, p, s);
   if (t1) return launch_cfg<1, 1>(cfg, p, s);
   // stride-2 data-gradient phases: two configurations only

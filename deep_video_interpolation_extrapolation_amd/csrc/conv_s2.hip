@@ -333,16 +333,10 @@ static void launch_s2(const dvie_conv_desc& p, hipStream_t s) {
     DVIE_LAUNCH((conv_s2_kernel<TM, 0, DW>), dim3(grid), dim3(C::NTH), 0, s, p, n_ct, n_tiles, tiles_x, tiles_y);
 }
 
-// DVIE_CONV_S2=0: stride-2 convs on the per-tap implicit GEMM (A/B runs); read per launch
-static bool s2_on() {
-  const char* e = getenv("DVIE_CONV_S2");
-  return !(e && *e == '0');
-}
-
 // stride-2 3x3 zero-padded forward conv, bf16 output, identity output placement; true when
 // the phase-split halo kernel took the launch
 bool conv_s2_launch(const dvie_conv_desc& p, hipStream_t s) {
-  if (!s2_on() || p.dtype != DVIE_BF16 || p.out_f32 || p.beta || p.dact) return false;
+  if (p.dtype != DVIE_BF16 || p.out_f32 || p.beta || p.dact) return false;
   if (p.sy != 2 || p.sx != 2 || p.th != 3 || p.tw != 3 || p.dy0 != -1 || p.dx0 != -1 || p.ddy != 1 || p.ddx != 1)
     return false;
   if (p.osy != 1 || p.osx != 1 || p.ory != 0 || p.orx != 0 || p.yh != p.oh || p.yw != p.ow) return false;

@@ -204,7 +204,8 @@ __device__ __forceinline__ void warp_dflow_terms(float a, float b, float c, floa
 //   WIN = 3: the side the fractional part f(c) = ix(c) - x0(c) points to, o.x + {-1 .. 1}
 //            for f < 1/2 (D(s) in {D - 1, D}), o.x + {-2 .. 0} otherwise: every sample with
 //            |delta(s) - delta(c)| < 1/2 px.
-// Samples a window misses (folding / discontinuous flow) are added with atomics.
+// Samples a window misses (folding / discontinuous flow) are added with atomics.  Only WIN = 4
+// is instantiated (a noisy flow stays off the atomic path).
 //
 // Three launches (one pixel per lane, a wave = 64 consecutive pixels of a row):
 //   tap   per sample: (ix, iy) into the workspace (8 B, exact fp32: every later weight is
@@ -305,6 +306,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tap_kernel(const dvie_warp_desc 
 // pull pass
 template <int WIN, int CC>
 __global__ __launch_bounds__(256) void warp_bwd_pull_kernel(const dvie_warp_desc p) {
+  static_assert(WIN == 4, "the contiguous-run loads below are written for the 4-wide window");
   constexpr int NC = WIN * WIN;
   const int waves = p.n * p.h * ((p.w + 63) >> 6);
   const int lane = threadIdx.x & 63;
@@ -335,8 +337,8 @@ __global__ __launch_bounds__(256) void warp_bwd_pull_kernel(const dvie_warp_desc
     for (int q = 0; q < NC; ++q)
       off[q] = rowok[q / WIN] && colok[q % WIN] ? (unsigned)(rowo[q / WIN] + q % WIN) : kWarpOOB;
     // wide: every lane's window columns lie inside the image (wave-uniform), so a window row
-    // is one contiguous run -- its taps one 16-B + one 8-B (WIN 3) or two 16-B loads, its
-    // dout values one 12-B / 16-B load per channel -- instead of one load per candidate
+    // is one contiguous run -- its taps two 16-B loads, its dout values one 16-B load per
+    // channel -- instead of one load per candidate
     // (these gathers are bound by vector-memory instructions, not bytes)
     const bool wide = __all(colok[0] && colok[WIN - 1]);
     float2 tq[NC];
@@ -347,13 +349,9 @@ __global__ __launch_bounds__(256) void warp_bwd_pull_kernel(const dvie_warp_desc
         const auto a = __builtin_amdgcn_raw_buffer_load_b128(rt, rb, 0, 0);
         tq[j * WIN] = make_float2(__uint_as_float(a[0]), __uint_as_float(a[1]));
         tq[j * WIN + 1] = make_float2(__uint_as_float(a[2]), __uint_as_float(a[3]));
-        if constexpr (WIN == 3) {
-          tq[j * WIN + 2] = warp_ld_tap(rt, rowok[j] ? rb + 16u : kWarpOOB);
-        } else {
-          const auto b = __builtin_amdgcn_raw_buffer_load_b128(rt, rowok[j] ? rb + 16u : kWarpOOB, 0, 0);
-          tq[j * WIN + 2] = make_float2(__uint_as_float(b[0]), __uint_as_float(b[1]));
-          tq[j * WIN + 3] = make_float2(__uint_as_float(b[2]), __uint_as_float(b[3]));
-        }
+        const auto b = __builtin_amdgcn_raw_buffer_load_b128(rt, rowok[j] ? rb + 16u : kWarpOOB, 0, 0);
+        tq[j * WIN + 2] = make_float2(__uint_as_float(b[0]), __uint_as_float(b[1]));
+        tq[j * WIN + 3] = make_float2(__uint_as_float(b[2]), __uint_as_float(b[3]));
       }
     } else {
 #pragma unroll
@@ -365,15 +363,9 @@ __global__ __launch_bounds__(256) void warp_bwd_pull_kernel(const dvie_warp_desc
 #pragma unroll
         for (int j = 0; j < WIN; ++j) {
           const unsigned rb = rowok[j] ? (unsigned)rowo[j] * 4u : kWarpOOB;
-          if constexpr (WIN == 3) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b96(rg, rb, 0, 0);
+          const auto v = __builtin_amdgcn_raw_buffer_load_b128(rg, rb, 0, 0);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) g[j * WIN + i] = __uint_as_float(v[i]);
-          } else {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rg, rb, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) g[j * WIN + i] = __uint_as_float(v[i]);
-          }
+          for (int i = 0; i < 4; ++i) g[j * WIN + i] = __uint_as_float(v[i]);
         }
       } else {
 #pragma unroll
@@ -542,36 +534,20 @@ int dvie_warp_fwd(const dvie_warp_desc* d, void* stream) {
   DVIE_CHECK_ARG(waves < (1LL << 31) && (long long)d->h * d->w < (1LL << 29), "warp: size");
   // waves per workgroup: 8 once the frames outgrow the L2s (8x3x1024x2048: 101.5 -> 95.5 us,
   // 0.66 -> 0.70 of HBM), 4 below (8x3x256x512: 7.5 vs 8.4 us; 16 loses at both sizes:
-  // profiles/r06/warp_wpb/).  DVIE_WARP_FWD_WPB (A/B, read per launch): 4 / 8 / 16
-  const char* we = getenv("DVIE_WARP_FWD_WPB");
-  const int wpb = we && *we ? atoi(we) : (waves >= 32768 ? 8 : 4);
-  DVIE_CHECK_ARG(wpb == 4 || wpb == 8 || wpb == 16, "warp: DVIE_WARP_FWD_WPB must be 4, 8 or 16");
+  // profiles/r06/warp_wpb/)
+  const int wpb = waves >= 32768 ? 8 : 4;
   // one workgroup per wpb waves (jobs) up to 8192 workgroups
-  int grid = (int)((waves + wpb - 1) / wpb < 8192 ? (waves + wpb - 1) / wpb : 8192);
-  if (const char* e = getenv("DVIE_WARP_FWD_GRID")) {  // A/B: blocks = min(jobs / 4, cap)
-    const long long need = (waves + 3) / 4, cap = atoi(e);
-    if (cap > 0) grid = (int)(need < cap ? need : cap);
-  }
-  // flow loads and output stores read / written once: non-temporal (aux 2).  Same box,
-  // 8x3x256x512 8.2 -> 7.4 us, 8x3x1024x2048 128.9 -> 121.5 us (profiles/r04warpnt/).
-  // DVIE_WARP_NT (A/B, read per launch): 0 = default policy, 1 = non-temporal stores only
-  const char* nt = getenv("DVIE_WARP_NT");
-  const int ntm = nt && *nt ? atoi(nt) : 2;
+  const int grid = (int)((waves + wpb - 1) / wpb < 8192 ? (waves + wpb - 1) / wpb : 8192);
   // XCD bands pay off once the frames outgrow the L2s: 8x3x1024x2048 121.0 -> 100.2 us
   // (0.555 -> 0.670 of HBM), while at 8x3x256x512 (12.6 MB) they cost 7.2 -> 8.6 us
-  // (profiles/r04aa/).  DVIE_WARP_XCD (A/B, read per launch): 1 = always, 0 = never
-  const char* xe = getenv("DVIE_WARP_XCD");
-  const int xcd = xe && *xe ? atoi(xe) : ((long long)d->n * d->c * d->h * d->w * 4 > (64ll << 20));
-  if (d->c == 3 && ntm == 2 && wpb == 8)
+  // (profiles/r04aa/)
+  const int xcd = (long long)d->n * d->c * d->h * d->w * 4 > (64ll << 20);
+  // three channels: flow loads and output stores read / written once, non-temporal (aux 2).
+  // Same box, 8x3x256x512 8.2 -> 7.4 us, 8x3x1024x2048 128.9 -> 121.5 us (profiles/r04warpnt/)
+  if (d->c == 3 && wpb == 8)
     DVIE_LAUNCH((warp_fwd_kernel<3, 2, 2, 8>), dim3(grid), dim3(512), 0, (hipStream_t)stream, *d, xcd);
-  else if (d->c == 3 && ntm == 2 && wpb == 16)
-    DVIE_LAUNCH((warp_fwd_kernel<3, 2, 2, 16>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, *d, xcd);
-  else if (d->c == 3 && ntm == 1)
-    DVIE_LAUNCH((warp_fwd_kernel<3, 0, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, xcd);
-  else if (d->c == 3 && ntm == 2)
-    DVIE_LAUNCH((warp_fwd_kernel<3, 2, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, xcd);
   else if (d->c == 3)
-    DVIE_LAUNCH(warp_fwd_kernel<3>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, xcd);
+    DVIE_LAUNCH((warp_fwd_kernel<3, 2, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, xcd);
   else
     DVIE_LAUNCH(warp_fwd_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, xcd);
   DVIE_RETURN_LAUNCH();
@@ -582,11 +558,6 @@ size_t dvie_warp_ws_floats(const dvie_warp_desc* d) {
   const size_t px = (size_t)d->n * d->h * d->w;
   return (2 * px + 3) / 4 * 4 + (px + 15) / 16 * 4;  // taps, far bytes (16-B aligned)
 }
-
-// pull window width (see warp_bwd_pull_kernel): 4 by default -- a noisy flow (a flow net early
-// in training) stays off the atomic path; DVIE_WARP_WIN=3 for A/B runs (15% faster on a
-// smooth flow, 22% slower with 0.2 px per-pixel noise at 1024x2048: profiles/r02_warp/)
-static const int warp_win_env = getenv("DVIE_WARP_WIN") && atoi(getenv("DVIE_WARP_WIN")) == 3 ? 3 : 4;
 
 int dvie_warp_bwd(const dvie_warp_desc* d, void* stream) {
   DVIE_CHECK_ARG(d && d->img && d->flow && d->dout && d->n > 0 && d->c > 0 && d->h > 0 && d->w > 0, "warp: args");
@@ -604,17 +575,13 @@ int dvie_warp_bwd(const dvie_warp_desc* d, void* stream) {
   else
     DVIE_LAUNCH(warp_bwd_tap_kernel<0>, dim3(grid), dim3(256), 0, s, *d);
   if (d->dimg) {
-    if (warp_win_env == 3) {
-      if (c3)
-        DVIE_LAUNCH((warp_bwd_pull_kernel<3, 3>), dim3(grid), dim3(256), 0, s, *d);
-      else
-        DVIE_LAUNCH((warp_bwd_pull_kernel<3, 0>), dim3(grid), dim3(256), 0, s, *d);
-    } else {
-      if (c3)
-        DVIE_LAUNCH((warp_bwd_pull_kernel<4, 3>), dim3(grid), dim3(256), 0, s, *d);
-      else
-        DVIE_LAUNCH((warp_bwd_pull_kernel<4, 0>), dim3(grid), dim3(256), 0, s, *d);
-    }
+    // pull window of 4: a noisy flow (a flow net early in training) stays off the atomic path
+    // (3 is 15% faster on a smooth flow, 22% slower with 0.2 px per-pixel noise at 1024x2048:
+    // profiles/r02_warp/)
+    if (c3)
+      DVIE_LAUNCH((warp_bwd_pull_kernel<4, 3>), dim3(grid), dim3(256), 0, s, *d);
+    else
+      DVIE_LAUNCH((warp_bwd_pull_kernel<4, 0>), dim3(grid), dim3(256), 0, s, *d);
     const long long quads = ((long long)d->n * d->h * d->w + 3) / 4;
     DVIE_LAUNCH(warp_bwd_far_kernel, dim3((unsigned)std::min<long long>((quads + 255) / 256, 4096)), dim3(256), 0, s, *d);
   }

@@ -738,13 +738,8 @@ __global__ __launch_bounds__(512) void wgrad_wide_kernel(const dvie_wgrad_desc p
     wgrad_wide_body<false>(p, smem, c0, k0, split, t_begin, t_end);
 }
 
-// diagnostic override, read once (plan-time slab counts and launches must agree):
-// DVIE_WGRAD_HALO=0 = per-tap kernel only
-static const bool wg_halo_env_off = getenv("DVIE_WGRAD_HALO") && *getenv("DVIE_WGRAD_HALO") == '0';
-
 static bool wgrad_halo_eligible(const dvie_wgrad_desc& p) {
   if (p.dtype != DVIE_BF16) return false;
-  if (wg_halo_env_off) return false;
   if (p.sy != 1 || p.sx != 1 || p.ddy != 1 || p.ddx != 1) return false;
   // (the 2 x 2 / 2 x 1 / 1 x 2 tap grids are the stride-2 phase launches' only: ws_taps > 0)
   if (!((p.th == 1 && p.tw == 1) || (p.th == 3 && p.tw == 3) || (p.ws_taps > 0 && p.th <= 2 && p.tw <= 2))) return false;
@@ -765,19 +760,11 @@ struct WgPlan {
   int pr, tmo, tmi, wide;
 };
 
-// DVIE_WG_NARROW=0: 3x3 layers with <= 32 output channels on the 8-wave kernel (A/B runs)
-static const bool wg_narrow_env_off = getenv("DVIE_WG_NARROW") && *getenv("DVIE_WG_NARROW") == '0';
-
-// DVIE_WG_WIDE=0: 1x1 wide layers on the 128 x 128 block kernel (A/B runs)
-static const bool wg_wide_env_off = getenv("DVIE_WG_WIDE") && *getenv("DVIE_WG_WIDE") == '0';
-
 static WgPlan wgrad_plan(const dvie_wgrad_desc& p) {
   // (the phase launches of one shared slab set all take this plan: equal tiles and splits)
   if (p.th > 1 || p.tw > 1 || p.ws_taps > 0) return {4, 1, 1, 0};
-  if (!wg_wide_env_off && p.ws_taps == 0 && p.c > 128 && p.cout > 128 && p.dy0 == 0 && p.dx0 == 0 && p.oh == p.ih && p.ow == p.iw)
+  if (p.c > 128 && p.cout > 128 && p.dy0 == 0 && p.dx0 == 0 && p.oh == p.ih && p.ow == p.iw)
     return {1, 4, 4, 1};
-  const char* e = getenv("DVIE_WG_TM");  // tuning override for 1x1: "<tmo><tmi>", e.g. "11"
-  if (e && e[0] && e[1]) return {2, e[0] == '2' ? 2 : 1, e[1] == '2' ? 2 : 1, 0};
   return {2, p.cout > 64 ? 2 : 1, p.c > 64 ? 2 : 1, 0};
 }
 
@@ -804,33 +791,23 @@ int wgrad_halo_splits(const dvie_wgrad_desc& p) {
   int tx, ty, nt, nco, nci;
   wgrad_tiles(p, w, tx, ty, nt, nco, nci);
   int s = 256 / (nco * nci);  // one workgroup per CU (LDS-bound): a single wave of workgroups
-  const char* e = getenv("DVIE_WG_SPLITS");  // tuning: multiplier of that split count (e.g. 0.5)
-  if (e && *e && atof(e) > 0) s = (int)(s * atof(e) + 0.5);
   if (s > nt) s = nt;
   return s < 1 ? 1 : s;
 }
 
-// one partial slab per split (the kernel sums its two row halves)
-// DVIE_WG_MERGE=0: two slabs per split, row halves unmerged (A/B runs)
-static const int wg_merge = getenv("DVIE_WG_MERGE") && *getenv("DVIE_WG_MERGE") == '0' ? 0 : 1;
-// timing-only ablation bits (DVIE_WG_DBG, -DDVIE_TIMING_DBG builds; read per launch)
-static int wg_dbg() {
+// wgrad_halo_kernel's runtime `flags`: the settled side of each retired A/B switch, passed as
+// constants (the kernel still branches on them; folding them in changes its ISA and is a
+// separate, measured change -- DESIGN.md)
+constexpr int WG_MERGE = 1;    // one partial slab per split: the kernel sums its two row halves
+constexpr int WG_SETPRIO = 0;  // (2 = raised priority for the upper waves: measured neutral, off)
+
 #ifdef DVIE_TIMING_DBG
+// timing-only ablation bits (DVIE_WG_DBG; read per launch)
+static int wg_dbg() {
   const char* e = getenv("DVIE_WG_DBG");
   return e && *e ? atoi(e) : 0;
-#else
-  return 0;
+}
 #endif
-}
-// DVIE_SETPRIO=1: s_setprio 1 for the second half of the waves in the halo conv / weight-gradient
-// kernels (A/B runs)
-static const int wg_setprio = getenv("DVIE_SETPRIO") && *getenv("DVIE_SETPRIO") == '1' ? 2 : 0;
-
-// DVIE_WG_PIPE (A/B, read per launch): 0 = 3x3 weight gradients without the fragment pipeline
-static bool wg_pipe_on() {
-  const char* e = getenv("DVIE_WG_PIPE");
-  return !(e && *e == '0');
-}
 
 // DVIE_WG_REUSE (A/B, read per launch): 0 = 3x3 weight gradients on the k-step fragment pipeline
 // (every tap's X fragment read per output row) instead of the row-walking reuse form
@@ -845,37 +822,35 @@ int wgrad_halo_bias_slabs(const dvie_wgrad_desc& p) {
   return wgrad_plan(p).wide ? p.splits : 2 * p.splits;
 }
 
-int wgrad_halo_slabs(const dvie_wgrad_desc& p) {
-  return wgrad_halo_eligible(p) && !wg_merge && !wgrad_plan(p).wide ? 2 * p.splits : p.splits;
-}
+// weight partial slabs: one per split, whichever kernel takes the launch
+int wgrad_halo_slabs(const dvie_wgrad_desc& p) { return p.splits; }
 
+// Selection by (tap grid, cout <= 32, bias sums wanted, reuse): the tap-grid kernels all run the
+// fragment pipeline (PIPE); the plain 1x1 layers pick their block shape from wgrad_plan.
 bool wgrad_halo_launch(const dvie_wgrad_desc& p, hipStream_t s) {
   if (!wgrad_halo_eligible(p)) return false;
   const WgPlan w = wgrad_plan(p);
   int tiles_x, tiles_y, n_tiles, n_co, n_ci;
   wgrad_tiles(p, w, tiles_x, tiles_y, n_tiles, n_co, n_ci);
   const int grid = n_co * n_ci * p.splits;
-  const bool wg_pipe = wg_pipe_on();
   if (w.wide) {
     DVIE_LAUNCH(wgrad_wide_kernel, dim3(grid), dim3(512), 0, s, p, n_co, n_ci, p.splits, n_tiles);
     return true;
   }
-#define DVIE_WG(TH, PR, TMO, TMI)                                                                                   \
-  DVIE_LAUNCH((wgrad_halo_kernel<TH, TH, PR, TMO, TMI>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci, p.splits, \
-                     tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio)
-  const bool wg_reuse = wg_reuse_on();
+#define DVIE_WG(NTH, ...)                                                                                      \
+  DVIE_LAUNCH((wgrad_halo_kernel<__VA_ARGS__>), dim3(grid), dim3(NTH), 0, s, p, n_co, n_ci, p.splits, tiles_x, \
+              tiles_y, n_tiles, WG_MERGE | WG_SETPRIO)
+  const bool reuse = wg_reuse_on(), bias = p.bws != nullptr;
 #ifdef DVIE_TIMING_DBG
-  if (p.th == 3 && p.cout > 32 && wg_pipe && wg_dbg()) {
+  if (p.th == 3 && p.cout > 32 && wg_dbg()) {
     switch (wg_dbg()) {
-#define DVIE_WG_AB(V)                                                                                               \
-  case V: {                                                                                                         \
-    if (wg_reuse)                                                                                                   \
-      DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, V, true, true>), dim3(grid), dim3(512), 0, s, p, n_co, \
-                  n_ci, p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);                                 \
-    else                                                                                                            \
-      DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, V>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,       \
-                  p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);                                       \
-    return true;                                                                                                    \
+#define DVIE_WG_AB(V)                                    \
+  case V: {                                              \
+    if (reuse)                                           \
+      DVIE_WG(512, 3, 3, 4, 1, 1, 8, true, V, true, true); \
+    else                                                 \
+      DVIE_WG(512, 3, 3, 4, 1, 1, 8, true, V);           \
+    return true;                                         \
   }
       DVIE_WG_AB(8) DVIE_WG_AB(16) DVIE_WG_AB(32) DVIE_WG_AB(64) DVIE_WG_AB(128) DVIE_WG_AB(136) DVIE_WG_AB(80)
       DVIE_WG_AB(192) DVIE_WG_AB(144) DVIE_WG_AB(72)
@@ -884,51 +859,44 @@ bool wgrad_halo_launch(const dvie_wgrad_desc& p, hipStream_t s) {
     }
   }
 #endif
-  // 3x3, 64 x 64 blocks: the row-walking fragment-reuse form (DVIE_WG_REUSE=0: the k-step form)
-  if (p.th == 3 && p.cout > 32 && wg_pipe && wg_reuse && !p.bws)
-    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, 0, false, true>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,
-                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-  else if (p.th == 3 && p.cout > 32 && wg_pipe && wg_reuse)
-    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, 0, true, true>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,
-                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-  else if (p.th == 3 && p.cout <= 32 && !wg_narrow_env_off && wg_reuse)
-    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 4, true, 0, true, true>), dim3(grid), dim3(256), 0, s, p, n_co, n_ci,
-                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-  else if (p.th == 3 && p.cout > 32 && wg_pipe && !p.bws)
-    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true, 0, false>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,
-                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-  else if (p.th == 3 && p.cout > 32 && wg_pipe)
-    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 8, true>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci, p.splits,
-                       tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-  // the stride-2 weight gradient's phase launches (ws_taps): 2 x 2, 2 x 1, 1 x 2 tap grids
-#define DVIE_WG2(TH, TW)                                                                                        \
-  else if (p.th == TH && p.tw == TW && !p.bws)                                                                  \
-    DVIE_LAUNCH((wgrad_halo_kernel<TH, TW, 4, 1, 1, 8, true, 0, false>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci, \
-                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);                                        \
-  else if (p.th == TH && p.tw == TW)                                                                            \
-    DVIE_LAUNCH((wgrad_halo_kernel<TH, TW, 4, 1, 1, 8, true>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci, p.splits, \
-                tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-  DVIE_WG2(2, 2) DVIE_WG2(2, 1) DVIE_WG2(1, 2)
-  else if (p.ws_taps > 0 && p.th == 1 && p.tw == 1 && !p.bws)
-    DVIE_LAUNCH((wgrad_halo_kernel<1, 1, 4, 1, 1, 8, true, 0, false>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci,
-                p.splits, tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-  else if (p.ws_taps > 0 && p.th == 1 && p.tw == 1)
-    DVIE_LAUNCH((wgrad_halo_kernel<1, 1, 4, 1, 1, 8, true>), dim3(grid), dim3(512), 0, s, p, n_co, n_ci, p.splits,
-                tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-#undef DVIE_WG2
-  else if (p.th == 3 && p.cout <= 32 && !wg_narrow_env_off)
-    DVIE_LAUNCH((wgrad_halo_kernel<3, 3, 4, 1, 1, 4, true>), dim3(grid), dim3(256), 0, s, p, n_co, n_ci, p.splits,
-                       tiles_x, tiles_y, n_tiles, wg_merge | wg_setprio);
-  else if (p.th == 3)
-    DVIE_WG(3, 4, 1, 1);
+  // 8 waves on a TH x TW tap grid, 64 x 64 blocks, with or without the bias column sums
+#define DVIE_WG_TAPS(TH, TW)                              \
+  else if (p.th == TH && p.tw == TW) {                    \
+    if (bias)                                             \
+      DVIE_WG(512, TH, TW, 4, 1, 1, 8, true);             \
+    else                                                  \
+      DVIE_WG(512, TH, TW, 4, 1, 1, 8, true, 0, false);   \
+  }
+  if (p.th == 3 && p.cout <= 32) {  // 4 waves: one 32-channel block
+    if (reuse)
+      DVIE_WG(256, 3, 3, 4, 1, 1, 4, true, 0, true, true);
+    else
+      DVIE_WG(256, 3, 3, 4, 1, 1, 4, true);
+  } else if (p.th == 3 && reuse) {  // the row-walking fragment-reuse form (DVIE_WG_REUSE=0: the k-step form)
+    if (bias)
+      DVIE_WG(512, 3, 3, 4, 1, 1, 8, true, 0, true, true);
+    else
+      DVIE_WG(512, 3, 3, 4, 1, 1, 8, true, 0, false, true);
+  }
+  DVIE_WG_TAPS(3, 3)
+  // the stride-2 weight gradient's phase launches (ws_taps): 2 x 2, 2 x 1, 1 x 2 and 1 x 1 tap grids
+  DVIE_WG_TAPS(2, 2) DVIE_WG_TAPS(2, 1) DVIE_WG_TAPS(1, 2)
+  else if (p.ws_taps > 0) {
+    if (bias)
+      DVIE_WG(512, 1, 1, 4, 1, 1, 8, true);
+    else
+      DVIE_WG(512, 1, 1, 4, 1, 1, 8, true, 0, false);
+  }
+#undef DVIE_WG_TAPS
+  // plain 1x1: two-row tiles, 64- or 128-channel blocks on either side
   else if (w.tmo == 2 && w.tmi == 2)
-    DVIE_WG(1, 2, 2, 2);
+    DVIE_WG(512, 1, 1, 2, 2, 2);
   else if (w.tmo == 2)
-    DVIE_WG(1, 2, 2, 1);
+    DVIE_WG(512, 1, 1, 2, 2, 1);
   else if (w.tmi == 2)
-    DVIE_WG(1, 2, 1, 2);
+    DVIE_WG(512, 1, 1, 2, 1, 2);
   else
-    DVIE_WG(1, 2, 1, 1);
+    DVIE_WG(512, 1, 1, 2, 1, 1);
 #undef DVIE_WG
   return true;
 }

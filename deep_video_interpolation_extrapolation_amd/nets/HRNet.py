@@ -12,7 +12,6 @@ Layout: activations NHWC in the compute dtype (fp32 parity mode or bf16), channe
 padded to multiples of 8; the 14-channel stem input is laid out as
 [segA(4) 0000 segB(4) 0000 rgb(6) 00] and the stem weights are packed to match.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -448,8 +447,7 @@ class HRNet(FlatParams, nn.Module):
             srcs = [E.R(t)] + srcs[3:]
         g.fuse(srcs, out, act=act)
 
-    # DVIE_FUSE_HEADS=0: the two 1x1 head convs as separate launches (A/B runs)
-    fuse_heads = os.environ.get("DVIE_FUSE_HEADS", "1") != "0"
+    fuse_heads = True  # False: the two 1x1 head convs as separate launches
     _stack_limit = 0xFFFFFF00  # bytes of one image of the stacked hidden map (32-bit buffer range)
 
     def _heads(self, g, cat):

@@ -1,7 +1,8 @@
-"""Time dvie_conv2d_fwd per tile configuration on HRNet-shaped convolutions and check each
-result against torch's fp32 conv2d of the same bf16-rounded operands.
+"""Time dvie_conv2d_fwd on HRNet- and VGG-shaped convolutions (the kernel the library picks,
+under whatever DVIE_* switches the environment sets) and check each result against torch's
+fp32 conv2d of the same bf16-rounded operands.
 
-    python tools/conv_tune.py [cfgs] [iters] [shape-substring]   e.g.  python tools/conv_tune.py -1,0,1 20 '64->64'   (several: '128->128|256->256')
+    python tools/conv_tune.py [iters] [shape-substring]   e.g.  python tools/conv_tune.py 20 '64->64'   (several: '128->128|256->256')
 """
 import ctypes
 import os
@@ -39,9 +40,8 @@ SHAPES = [  # name, cin, cout, k, H, W, batch
 
 
 def main():
-    cfgs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "-1,-3").split(",")]
-    iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-    only = sys.argv[3] if len(sys.argv) > 3 else ""
+    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+    only = sys.argv[2] if len(sys.argv) > 2 else ""
     lib = L.load()
     dev = torch.device("cuda:0")
     s = L.stream_ptr()
@@ -67,30 +67,27 @@ def main():
         d.yh, d.yw, d.osy, d.osx, d.ory, d.orx = H, W, 1, 1, 0, 0
         d.dtype, d.out_f32, d.alpha = L.BF16, int(out_f32), 0.2
         flops = 2.0 * B * H * W * cout * cin * k * k
-        for cfg in cfgs:
-            os.environ["DVIE_CONV_CFG"] = "" if cfg == -3 else str(cfg)
-            y.zero_()
-            rc = lib.dvie_conv2d_fwd(ctypes.byref(d), ctypes.c_void_p(s))
-            if rc:
-                print(f"{name:28s} cfg {cfg:2d}: rc {rc} {lib.dvie_last_error()}")
-                continue
-            torch.cuda.synchronize()
-            err = ((y.float() - ref).abs().max() / ref.abs().max()).item()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            # warm-up long enough for the clocks to settle: with 3 launches the first config
-            # timed in a process read ~8% slow (r01zd), which reorders close configs
-            for _ in range(max(3, 4 * iters) if first else 3):
-                lib.dvie_conv2d_fwd(ctypes.byref(d), ctypes.c_void_p(s))
-            e0.record()
-            for _ in range(iters):
-                lib.dvie_conv2d_fwd(ctypes.byref(d), ctypes.c_void_p(s))
-            e1.record()
-            torch.cuda.synchronize()
-            first = False
-            ms = e0.elapsed_time(e1) / iters
-            print(f"{name:28s} cfg {cfg:2d}: {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TF/s  relerr {err:.2e}"
-                  f"{'  BAD' if err > 1e-2 else ''}", flush=True)
-    os.environ.pop("DVIE_CONV_CFG", None)
+        y.zero_()
+        rc = lib.dvie_conv2d_fwd(ctypes.byref(d), ctypes.c_void_p(s))
+        if rc:
+            print(f"{name:28s}: rc {rc} {lib.dvie_last_error()}")
+            continue
+        torch.cuda.synchronize()
+        err = ((y.float() - ref).abs().max() / ref.abs().max()).item()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        # warm-up long enough for the clocks to settle: with 3 launches the first shape
+        # timed in a process read ~8% slow (r01zd)
+        for _ in range(max(3, 4 * iters) if first else 3):
+            lib.dvie_conv2d_fwd(ctypes.byref(d), ctypes.c_void_p(s))
+        e0.record()
+        for _ in range(iters):
+            lib.dvie_conv2d_fwd(ctypes.byref(d), ctypes.c_void_p(s))
+        e1.record()
+        torch.cuda.synchronize()
+        first = False
+        ms = e0.elapsed_time(e1) / iters
+        print(f"{name:28s}: {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TF/s  relerr {err:.2e}"
+              f"{'  BAD' if err > 1e-2 else ''}", flush=True)
 
 
 if __name__ == "__main__":
