@@ -145,6 +145,16 @@ class SynthBridgeDesc(ctypes.Structure):
     ]
 
 
+class SynthScoreDesc(ctypes.Structure):
+    _fields_ = [
+        ("pred", vp), ("gt", vp), ("pred_label", vp), ("gt_label", vp),
+        ("sse", vp), ("ssim", vp), ("agree", vp), ("valid", vp), ("inter", vp), ("uni", vp), ("ws", vp),
+        ("pred_s0", i64), ("pred_s1", i64), ("gt_s0", i64), ("gt_s1", i64),
+        ("pred_label_s0", i64), ("pred_label_s1", i64), ("gt_label_s0", i64), ("gt_label_s1", i64),
+        ("n0", i32), ("n1", i32), ("h", i32), ("w", i32), ("n_classes", i32), ("pad0", i32),
+    ]
+
+
 class BnDesc(ctypes.Structure):
     _fields_ = [
         ("x", vp), ("y", vp), ("g", vp), ("dx", vp), ("gamma", vp), ("beta", vp), ("dgamma", vp), ("dbeta", vp),
@@ -248,7 +258,7 @@ class Op(ctypes.Structure):
 _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, OP_COLSUM: ColsumDesc,
         OP_EW: EwDesc, OP_LOSS: LossDesc, OP_PACK: PackDesc, OP_BN_FWD: BnDesc, OP_HEAD_FWD: HeadDesc,
         OP_ATTN: AttnDesc, OP_HEAD3_BWD: Head3BwdDesc, OP_SEGENC_FWD: SegencDesc, OP_SEGENC_BWD: SegencBwdDesc, OP_WREDUCE_MULTI: WreduceMultiDesc, 100: WarpDesc, 101: SoftmaxDesc, 102: SnLayer, 103: ClipDesc,
-        104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc}
+        104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc, 107: SynthScoreDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -259,7 +269,7 @@ EXPORTS = [
     "dvie_reparam_bwd", "dvie_warp_ws_floats", "dvie_clip_prep", "dvie_attn", "dvie_step_inc", "dvie_adamax_dev",
     "dvie_adam_dev", "dvie_mfma_probe", "dvie_launch_probe", "dvie_sum_f32", "dvie_wgrad_bias_slabs", "dvie_head3_bwd",
     "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_pack_blocks", "dvie_trace_kernels", "dvie_traced_kernels",
-    "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge",
+    "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_score_ws_bytes",
 ]
 
 _lib = None
@@ -295,7 +305,7 @@ def load():
                      "dvie_loss", "dvie_warp_fwd", "dvie_warp_bwd", "dvie_bn_fwd", "dvie_bn_bwd", "dvie_head_fwd",
                      "dvie_head_bwd", "dvie_softmax_fwd", "dvie_softmax_bwd", "dvie_clip_prep", "dvie_attn",
                      "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
-                     "dvie_synth_bridge"):
+                     "dvie_synth_bridge", "dvie_synth_score"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]
@@ -315,6 +325,8 @@ def load():
         lib.dvie_warp_ws_floats.restype = ctypes.c_size_t
         lib.dvie_loss_ws_floats.argtypes = [vp]
         lib.dvie_loss_ws_floats.restype = ctypes.c_size_t
+        lib.dvie_synth_score_ws_bytes.argtypes = [vp]
+        lib.dvie_synth_score_ws_bytes.restype = ctypes.c_size_t
         lib.dvie_adamax.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]
         lib.dvie_scale.argtypes = [vp, i64, f32, vp]
         lib.dvie_adam.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]

@@ -789,6 +789,7 @@ size_t dvie_abi_sizeof(int which) {
     case 104: return sizeof(dvie_synth_load_desc);
     case 105: return sizeof(dvie_synth_finish_desc);
     case 106: return sizeof(dvie_synth_bridge_desc);
+    case 107: return sizeof(dvie_synth_score_desc);
     default: return 0;
   }
 }

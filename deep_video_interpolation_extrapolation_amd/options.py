@@ -10,6 +10,12 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
                             input_w; val: whole frames)
   --synth_levels K          --split test, INTER: frame-rate doublings of the recursive
                             interpolation (K levels: 2**K - 1 new frames between two inputs)
+  --synth_eval              --split test: held-out scoring instead of synthesis.  INTER keeps every
+                            2**K-th frame of a clip (K = --synth_levels), synthesises the others and
+                            scores them against the originals; EXTRA predicts up to --num_pred_step
+                            frames from a clip's first two and scores them against the frames that
+                            follow.  Writes <cycgen_load_dir>/synth_eval/scores.json (per clip and slot
+                            PSNR, SSIM, label accuracy, mIoU; the mean summary), no PNGs
 """
 import argparse
 
@@ -64,6 +70,7 @@ GLOBAL = [
     ("--synthetic", "synthetic", int, 0, None),
     ("--clip_store", "clip_store", str, None, None),
     ("--synth_levels", "synth_levels", int, 1, None),
+    ("--synth_eval", "synth_eval", bool, False, None),
 ]
 
 # second-stage flags of the reference's INTER sub-command (options/options.py:296-380);

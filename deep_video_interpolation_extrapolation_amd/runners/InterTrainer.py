@@ -365,6 +365,8 @@ class InterTrainer:
         a = self.args
         assert self.rank == 0, "test runs on one worker"
         assert a.cycgen_load_dir is not None, "please specify --cycgen_load_dir"
+        if getattr(a, "synth_eval", False):
+            return self.test_eval()
         syn = VideoSynthesizer(self.model.module, max_batch=max(1, a.batch_size))
         img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
         root = os.path.join(a.cycgen_load_dir, "synth")
@@ -383,6 +385,56 @@ class InterTrainer:
                 os.makedirs(d, exist_ok=True)
                 for k in range(arr.shape[0]):
                     Image.fromarray(np.ascontiguousarray(arr[k])).save(os.path.join(d, "{:04d}.png".format(k)))
+        return root
+
+    def _score(self, syn, frames, labels, clip):
+        """--split test --synth_eval, interpolation: every 2**synth_levels-th frame is kept, the
+        others are synthesised and scored (None: the clip is too short)"""
+        step = 1 << getattr(self.args, "synth_levels", 1)
+        T = frames.shape[1]
+        keep = (T - 1) // step * step + 1
+        if keep <= step:
+            self.log.info(f"synth_eval: skip {clip}: {T} frames, {step + 1} needed for --synth_levels")
+            return None
+        if keep < T:
+            self.log.info(f"synth_eval: {clip}: the last {T - keep} of {T} frames dropped ((T - 1) % {step} != 0)")
+        return syn.score_interpolation(frames[:, :keep], labels[:, :keep], levels=getattr(self.args, "synth_levels", 1))
+
+    def test_eval(self):
+        """--split test --synth_eval: the clips of test(), scored instead of written.  Per clip
+        VideoSynthesizer.score_interpolation / score_extrapolation (_score) against the clip's own
+        held-out frames -> <cycgen_load_dir>/synth_eval/scores.json: {"clips": {clip: {"slots",
+        "psnr", "ssim", "acc", "miou"}} (one value per scored slot), "summary": the means over
+        every scored frame of every clip and per position (synth.summarize)}; the summary also
+        goes to the log.  No PNG is written."""
+        import numpy as np
+        from PIL import Image
+        from ..synth import VideoSynthesizer, summarize
+        a = self.args
+        syn = VideoSynthesizer(self.model.module, max_batch=max(1, a.batch_size))
+        img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
+        clips, cols = {}, [[] for _ in range(5)]
+        for clip in sorted(d for d in os.listdir(img_dir) if os.path.isdir(os.path.join(img_dir, d))):
+            names = sorted(f for f in os.listdir(os.path.join(img_dir, clip)) if f.lower().endswith(".png"))
+            if not names:
+                self.log.info(f"synth_eval: skip {clip}: no frames")
+                continue
+            imgs = np.stack([np.asarray(Image.open(os.path.join(img_dir, clip, f)).convert("RGB")) for f in names])
+            labs = np.stack([np.asarray(Image.open(os.path.join(seg_dir, clip, f)).convert("L")) for f in names])
+            sc = self._score(syn, torch.from_numpy(imgs)[None].to(self.device), torch.from_numpy(labs)[None].to(self.device),
+                             clip)
+            if sc is None:
+                continue
+            vals = [v[0] for v in sc.host()]  # psnr, ssim, acc, miou of the one clip
+            clips[clip] = dict(slots=sc.slots, **{k: v.tolist() for k, v in zip(("psnr", "ssim", "acc", "miou"), vals)})
+            for col, v in zip(cols, [np.asarray(sc.positions)] + vals):
+                col.append(v)
+        res = dict(clips=clips, summary=summarize(*[np.concatenate(c) for c in cols]) if clips else None)
+        root = os.path.join(a.cycgen_load_dir, "synth_eval")
+        os.makedirs(root, exist_ok=True)
+        with open(os.path.join(root, "scores.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        self.log.info("synth_eval: {} clips, summary {}".format(len(clips), json.dumps(res["summary"])))
         return root
 
     def _scalars(self, tag, info):

@@ -58,6 +58,18 @@ def midpoint_schedule(T, levels):
     return out
 
 
+def heldout_slots(T, levels):
+    """Held-out scoring of a T-frame clip by `levels` doublings: frames 0, 2**levels, ... are
+    the inputs of the interpolation, every other time index is synthesised and scored against
+    the original -> those indices, ascending.  Needs (T - 1) % 2**levels == 0 and T > 2**levels
+    (ValueError otherwise)."""
+    step = 1 << max(levels, 1)
+    if levels < 1 or T <= step or (T - 1) % step:
+        raise ValueError(f"held-out interpolation of T={T} frames by levels={levels} needs levels >= 1, "
+                         f"(T - 1) % 2**levels == 0 and T > 2**levels")
+    return [t for t in range(T) if t % step]
+
+
 def synth_load(frames, out):
     """uint8 RGB frames (..., 3), contiguous -> fp32 `out` (..., ld) (dvie_synth_load)."""
     L.require_gpu(frames)
@@ -103,6 +115,156 @@ def synth_finish(rgb=None, seg=None, frame=None, label=None, n_classes=20):
         d.seg, d.label, d.seg_ld, d.n_classes = seg.data_ptr(), label.data_ptr(), seg.shape[-1], n_classes
     d.npix = ref.numel() // ref.shape[-1]
     L.check(L.load().dvie_synth_finish(ctypes.byref(d), L.stream_ptr(ref.device)), "synth finish")
+
+
+class FrameScores:
+    """Per-frame scores of uint8 frames against the originals (frame_scores): device tensors
+    shaped like the leading dimensions of the frames -- sse (int64), ssim (float64) and, with
+    label maps, agree, valid (int64), inter, uni (int64, a trailing class dimension); None
+    without.  psnr / acc / miou are derived on the device in float64."""
+    FIELDS = ("sse", "ssim", "agree", "valid", "inter", "uni")
+
+    def __init__(self, H, W, sse, ssim, agree=None, valid=None, inter=None, uni=None):
+        self.H, self.W = H, W
+        self.sse, self.ssim, self.agree, self.valid, self.inter, self.uni = sse, ssim, agree, valid, inter, uni
+
+    @property
+    def psnr(self):
+        """10 log10(255^2 / mse) per frame; +inf where the frames are equal (losses.py:103-116)"""
+        return 10.0 * torch.log10((255.0 ** 2 * 3 * self.H * self.W) / self.sse.double())
+
+    @property
+    def acc(self):
+        """pixel accuracy: the reference's `IoU` (losses.py:122-131)"""
+        if self.agree is None:
+            return None
+        # (a tensor divisor: torch turns a division by a Python scalar into a multiplication)
+        return self.agree.double() / torch.full_like(self.agree, self.H * self.W, dtype=torch.float64)
+
+    @property
+    def miou(self):
+        """mean of inter / uni over the classes with uni > 0 (NaN for a frame without a valid pixel)"""
+        if self.uni is None:
+            return None
+        seen = self.uni > 0
+        iou = torch.where(seen, self.inter.double() / self.uni.clamp(min=1).double(), torch.zeros((), dtype=torch.float64,
+                                                                                                  device=self.uni.device))
+        return iou.sum(-1) / seen.sum(-1).double()
+
+    def map(self, fn):
+        """the same scores with fn applied to every tensor (the class dimension stays last)"""
+        return FrameScores(self.H, self.W, *[None if getattr(self, k) is None else fn(getattr(self, k)) for k in self.FIELDS])
+
+
+def _lead_of(t, tail, what):
+    """(n0, n1, s0, s1) of `t` (..., *tail): up to two leading dimensions of any strides (in
+    elements = bytes), the trailing `tail` dimensions contiguous"""
+    k = len(tail)
+    if t.dtype != torch.uint8 or t.dim() < k or t.dim() > k + 2 or tuple(t.shape[t.dim() - k:]) != tuple(tail):
+        raise ValueError(f"{what}: uint8 (..., {', '.join(map(str, tail))}) with at most two leading dimensions, got "
+                         f"{tuple(t.shape)} {t.dtype}")
+    want = 1
+    for d in range(t.dim() - 1, t.dim() - k - 1, -1):
+        if t.shape[d] != 1 and t.stride(d) != want:
+            raise ValueError(f"{what}: the {k} frame-level dimensions must be contiguous, got strides {t.stride()}")
+        want *= t.shape[d]
+    lead = [(t.shape[d], t.stride(d)) for d in range(t.dim() - k)]
+    (n0, s0), (n1, s1) = ([(1, 0)] * (2 - len(lead)) + lead)
+    return n0, n1, s0, s1
+
+
+def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20):
+    """Score uint8 device frames `pred` (..., H, W, 3) against `gt` and, when both are given,
+    label maps `pred_labels` (..., H, W) against `gt_labels` (dvie_synth_score: one fused pass
+    and a finalize launch, no host synchronisation) -> FrameScores shaped like the leading
+    dimensions.  Up to two leading dimensions, of any strides (the (B, S) views interpolate /
+    extrapolate return are scored in place); the frame-level dimensions must be contiguous."""
+    L.require_gpu(pred)
+    if pred.dim() < 3 or pred.shape[-1] != 3:
+        raise ValueError(f"pred: uint8 (..., H, W, 3), got {tuple(pred.shape)}")
+    lead, (H, W) = tuple(pred.shape[:-3]), pred.shape[-3:-1]
+    if H < 1 or W < 1 or any(n < 1 for n in lead):
+        raise ValueError(f"pred: empty dimensions in {tuple(pred.shape)}")
+    if (pred_labels is None) != (gt_labels is None):
+        raise ValueError("pred_labels and gt_labels must be given together")
+    has_labels = pred_labels is not None
+    if has_labels and not 1 <= n_classes <= 32:
+        raise ValueError(f"n_classes={n_classes} must be in 1..32")
+    d = L.SynthScoreDesc()
+    d.n0, d.n1, d.pred_s0, d.pred_s1 = _lead_of(pred, (H, W, 3), "pred")
+    for t, tail, what in ((gt, (H, W, 3), "gt"),) + (((pred_labels, (H, W), "pred_labels"),
+                                                       (gt_labels, (H, W), "gt_labels")) if has_labels else ()):
+        if not isinstance(t, torch.Tensor) or t.device != pred.device or tuple(t.shape[:t.dim() - len(tail)]) != lead:
+            raise ValueError(f"{what}: a tensor on {pred.device} with the leading dimensions {lead} of pred")
+        _, _, s0, s1 = _lead_of(t, tail, what)
+        setattr(d, what.replace("labels", "label") + "_s0", s0)
+        setattr(d, what.replace("labels", "label") + "_s1", s1)
+    d.pred, d.gt, d.h, d.w, d.n_classes = pred.data_ptr(), gt.data_ptr(), H, W, n_classes
+    dev = pred.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = FrameScores(H, W, torch.empty(lead, **i64), torch.empty(lead, dtype=torch.float64, device=dev))
+    d.sse, d.ssim = out.sse.data_ptr(), out.ssim.data_ptr()
+    if has_labels:
+        d.pred_label, d.gt_label = pred_labels.data_ptr(), gt_labels.data_ptr()
+        out.agree, out.valid = torch.empty(lead, **i64), torch.empty(lead, **i64)
+        out.inter, out.uni = torch.empty(lead + (n_classes,), **i64), torch.empty(lead + (n_classes,), **i64)
+        d.agree, d.valid, d.inter, d.uni = (t.data_ptr() for t in (out.agree, out.valid, out.inter, out.uni))
+    lib = L.load()
+    ws = torch.empty((lib.dvie_synth_score_ws_bytes(ctypes.byref(d)),), dtype=torch.uint8, device=dev)
+    d.ws = ws.data_ptr()
+    L.check(lib.dvie_synth_score(ctypes.byref(d), L.stream_ptr(dev)), "synth score")
+    return out
+
+
+def summarize(position, psnr, ssim, acc, miou):
+    """Host-side means of per-frame scores (numpy arrays of one length; `position` an integer
+    per frame) -> {"psnr", "ssim", "acc", "miou", "frames", "per_position": {position: the same
+    four and "frames"}} as Python floats.  The mean PSNR is the mean of the per-frame PSNRs
+    (losses.py:103-116); an infinite value stays infinite."""
+    import numpy as np
+    position = np.asarray(position)
+    cols = dict(psnr=np.asarray(psnr, dtype=np.float64), ssim=np.asarray(ssim, dtype=np.float64),
+                acc=np.asarray(acc, dtype=np.float64), miou=np.asarray(miou, dtype=np.float64))
+
+    def means(sel):
+        with np.errstate(invalid="ignore"):
+            row = {k: float(np.mean(v[sel])) for k, v in cols.items()}
+        row["frames"] = int(np.count_nonzero(sel))
+        return row
+
+    out = means(np.ones(position.shape, dtype=bool))
+    out["per_position"] = {int(p): means(position == p) for p in sorted(set(position.tolist()))}
+    return out
+
+
+class SynthScores:
+    """What score_interpolation / score_extrapolation return: `slots`, the scored time indices
+    (interpolation: indices into the clip; extrapolation: the step index k of original frame
+    2 + k); `scores`, the FrameScores of shape (B, len(slots)), whose tensors and derived
+    values are also attributes here (sse, ssim, agree, valid, inter, uni, psnr, acc, miou);
+    `frames` / `labels`, the synthesised video as interpolate / extrapolate returns it;
+    `positions`, per slot the position the summary groups by (slot % 2**levels, or the step)."""
+
+    def __init__(self, slots, positions, scores, frames, labels):
+        self.slots, self.positions, self.scores, self.frames, self.labels = list(slots), list(positions), scores, frames, labels
+
+    def __getattr__(self, name):
+        if name in FrameScores.FIELDS or name in ("psnr", "acc", "miou"):
+            return getattr(self.scores, name)
+        raise AttributeError(name)
+
+    def host(self):
+        """psnr, ssim, acc, miou as float64 numpy arrays (B, len(slots)): one copy to the host"""
+        s = self.scores
+        return tuple(torch.stack([s.psnr, s.ssim, s.acc, s.miou]).cpu().numpy())
+
+    def summary(self):
+        """Means over all scored frames and per position (summarize) as Python floats -- the
+        one place that copies to the host."""
+        import numpy as np
+        psnr, ssim, acc, miou = self.host()
+        pos = np.broadcast_to(np.asarray(self.positions), psnr.shape)
+        return summarize(pos.ravel(), psnr.ravel(), ssim.ravel(), acc.ravel(), miou.ravel())
 
 
 class _Captured:
@@ -348,3 +510,36 @@ class VideoSynthesizer:
         fr, lb = self._roll(frames, labels, 2 + steps, [0, 1], [[(k, k + 1, k + 2)] for k in range(steps)],
                             keep=lambda s: s <= steps)
         return fr[2:].transpose(0, 1), lb[2:].transpose(0, 1)
+
+    # ---------------- held-out scoring ----------------
+    def score_interpolation(self, frames, labels, levels=1):
+        """Held-out scoring of interpolation: frames (B, T, H, W, 3) and labels (B, T, H, W) of
+        real clips with (T - 1) % 2**levels == 0 and T > 2**levels.  Frames 0, 2**levels, ...
+        go through interpolate(..., levels); every other slot t is scored against original
+        frame and label map t (heldout_slots) -> SynthScores, tensors (B, len(slots)).  The
+        slots at one offset inside the period are one strided (B, G) view of the synthesised
+        and of the original video, scored in place: 2**levels - 1 scoring calls."""
+        self._check(frames, labels)
+        T, step = frames.shape[1], 1 << max(levels, 0)
+        slots = heldout_slots(T, levels)
+        out_f, out_l = self.interpolate(frames[:, ::step], labels[:, ::step], levels)
+        parts = [frame_scores(out_f[:, o::step], frames[:, o::step], out_l[:, o::step], labels[:, o::step],
+                              n_classes=self.cm.n_classes) for o in range(1, step)]
+        # (B, G) per offset -> (B, G, step - 1) -> (B, G * (step - 1)): ascending slots
+        scores = parts[0].map(lambda _: None)
+        for k in FrameScores.FIELDS:
+            t = torch.stack([getattr(p, k) for p in parts], dim=2)
+            setattr(scores, k, t.reshape((t.shape[0], len(slots)) + tuple(t.shape[3:])))
+        return SynthScores(slots, [t % step for t in slots], scores, out_f, out_l)
+
+    def score_extrapolation(self, frames, labels):
+        """Held-out scoring of extrapolation: frames (B, 2 + S, H, W, 3), S >= 1.  The first two
+        frames are the inputs of extrapolate(..., steps=S); step k is scored against original
+        frame 2 + k -> SynthScores with slots 0 .. S-1, tensors (B, S)."""
+        self._check(frames, labels)
+        S = frames.shape[1] - 2
+        if S < 1:
+            raise ValueError("score_extrapolation needs two input frames and at least one frame of truth")
+        out_f, out_l = self.extrapolate(frames[:, :2], labels[:, :2], steps=S)
+        scores = frame_scores(out_f, frames[:, 2:], out_l, labels[:, 2:], n_classes=self.cm.n_classes)
+        return SynthScores(range(S), range(S), scores, out_f, out_l)

@@ -848,11 +848,63 @@ typedef struct dvie_synth_bridge_desc {
 
 int dvie_synth_bridge(const dvie_synth_bridge_desc* d, void* stream);
 
+/*
+ * dvie_synth_score: per-frame quality of synthesised uint8 frames / label maps against the
+ * frames that were really there (synth.frame_scores, VideoSynthesizer.score_interpolation /
+ * score_extrapolation).  One fused pass over the 8 B per pixel of two RGB frames and two label
+ * maps replaces, on the 8-bit data, the reference's losses.py:18-48 and 63-87 (gaussian,
+ * create_window, _ssim, SSIM), 103-116 (PSNR: the squared error it needs) and 122-131 (IoU).
+ *
+ * Frames: N = n0 * n1 frame pairs, frame (i0, i1) of a tensor at base + i0*s0 + i1*s1 BYTES
+ * (strides may be anything, a transposed (B, S) view of slot-major storage included); a frame is
+ * a contiguous h*w*3 block of uint8 RGB, a label map a contiguous h*w block of uint8.  No
+ * alignment of frame bases or rows is assumed.  pred_label / gt_label: both or neither.
+ * Outputs, indexed f = i0*n1 + i1, all written by the call (nothing is accumulated into):
+ *   sse[f]    int64   sum over the h*w*3 bytes of (pred - gt)^2, exact.  Width: a thread sums at
+ *                     most 32 squares <= 65025 and a block 192 such threads (< 4.0e8) in
+ *                     uint32; the per-frame sum over blocks is int64 (4096x8192: 6.6e12).
+ *   ssim[f]   float64 mean over pixels and the 3 channels of the reference's SSIM map of x/255:
+ *                     11-tap gaussian (sigma 1.5, normalised in float64), zero padding (samples
+ *                     outside the image are 0, the window is not renormalised), C1 = 0.01^2,
+ *                     C2 = 0.03^2.  Evaluated separably in float64 on the byte values with the
+ *                     constants scaled by 255^2.
+ *   agree[f]  int64   pixels with pred_label == gt_label (bytes as they are): losses.py IoU,
+ *                     a pixel accuracy, times h*w.
+ *   valid[f]  int64   pixels with gt_label < n_classes.
+ *   inter[f][c], uni[f][c] (c < n_classes, int64): over valid pixels, pred == c && gt == c and
+ *                     pred == c || gt == c.  A pred label >= n_classes matches no class.
+ * Without label maps only sse and ssim are written (the other four may be NULL).
+ * Bitwise reproducible: per-block partials (SSIM float64, counts integer) in the workspace,
+ * summed in a fixed order by one finalize launch; no float atomics; no intermediate image.
+ * ws: dvie_synth_score_ws_bytes(d) bytes, 8-byte aligned, fully overwritten (0 bytes for a
+ * descriptor whose sizes are invalid).  sse .. uni 8-byte aligned.  h, w >= 1, 1 <= n_classes
+ * <= 32, n0, n1 >= 1, n0 * n1 <= 65535.
+ */
+typedef struct dvie_synth_score_desc {
+  const uint8_t* pred;
+  const uint8_t* gt;
+  const uint8_t* pred_label;
+  const uint8_t* gt_label;
+  long long* sse;
+  double* ssim;
+  long long* agree;
+  long long* valid;
+  long long* inter;
+  long long* uni;
+  void* ws;
+  long long pred_s0, pred_s1, gt_s0, gt_s1;                         /* byte strides of (i0, i1) */
+  long long pred_label_s0, pred_label_s1, gt_label_s0, gt_label_s1;
+  int n0, n1, h, w, n_classes, pad0;
+} dvie_synth_score_desc;
+
+size_t dvie_synth_score_ws_bytes(const dvie_synth_score_desc* d);
+int dvie_synth_score(const dvie_synth_score_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
- * synth_bridge). */
+ * synth_bridge, synth_score). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

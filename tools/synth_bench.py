@@ -14,7 +14,13 @@
   rollout through the module forward plus torch glue, at 8x256x512 (n_scales 1) and
   1x1024x2048 (n_scales 3).
 
-    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json] [--two-stage]
+* held-out scoring (--score): us per call and GB/s of algorithmic bytes (8 B per pixel: two RGB
+  frames, two label maps) of synth.frame_scores at 8x256x512 and 1x1024x2048, against the same
+  scores composed from the public ops there were before it (torch uint8 -> fp32 NCHW, then
+  losses.SSIM, losses.PSNR and losses.IoU, one frame at a time), rotating over buffer sets
+  that exceed the 256 MiB Infinity Cache, and next to one batch-8 forward.
+
+    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json] [--two-stage | --score]
 """
 import argparse
 import json
@@ -29,8 +35,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deep_video_interpolation_extrapolation_amd import engine as E  # noqa: E402
 from deep_video_interpolation_extrapolation_amd import nets  # noqa: E402
 from deep_video_interpolation_extrapolation_amd.runners.InterTrainer import InterTrainer  # noqa: E402
-from deep_video_interpolation_extrapolation_amd.synth import (VideoSynthesizer, synth_bridge, synth_finish,  # noqa: E402
-                                                              synth_load)
+from deep_video_interpolation_extrapolation_amd import losses  # noqa: E402
+from deep_video_interpolation_extrapolation_amd.synth import (VideoSynthesizer, frame_scores, synth_bridge,  # noqa: E402
+                                                              synth_finish, synth_load)
 
 
 def make_net(large=False):
@@ -153,6 +160,67 @@ def bridge_numbers(dev, seconds):
     return out
 
 
+def composed_scores(pred, gt, pl, gl, ssim=losses.SSIM(), psnr=losses.PSNR(), iou=losses.IoU()):
+    """the baseline of --score: per frame, uint8 -> fp32 [0, 1] NCHW in torch, then the public
+    metric ops (1 - SSIM, PSNR, pixel accuracy; no per-class counts)"""
+    out = []
+    with torch.no_grad():
+        for k in range(pred.shape[0]):
+            a = pred[k:k + 1].permute(0, 3, 1, 2).float() / 255
+            b = gt[k:k + 1].permute(0, 3, 1, 2).float() / 255
+            out.append((ssim(a, b), psnr(a, b), iou(pl[k:k + 1], gl[k:k + 1])))
+    return out
+
+
+def score_numbers(dev, seconds):
+    """frame_scores against composed_scores, alternating, three rounds each; plus one batch-8
+    forward (extrapolate one step, 8x256x512 bf16, eager) for scale"""
+    out = {}
+    for n, H, W in ((8, 256, 512), (1, 1024, 2048)):
+        npix = n * H * W
+        sets = (320 << 20) // (8 * npix) + 1  # 8 B per pixel and set: more than the cache holds
+        pred, gt = ([torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(sets)]
+                    for _ in range(2))
+        pl, gl = ([torch.randint(0, 20, (n, H, W), dtype=torch.uint8, device=dev) for _ in range(sets)] for _ in range(2))
+        k = [0]
+
+        def fused():
+            i = k[0] = (k[0] + 1) % sets
+            frame_scores(pred[i], gt[i], pl[i], gl[i])
+
+        def composed():
+            i = k[0] = (k[0] + 1) % sets
+            composed_scores(pred[i], gt[i], pl[i], gl[i])
+
+        legs = dict(fused=fused, composed=composed)
+        for fn in legs.values():
+            fn()
+            fn()
+        rates = {name: [] for name in legs}
+        for _ in range(3):  # alternating
+            for name, fn in legs.items():
+                rates[name].append(timed(fn, seconds))
+        row = {name: dict(us=1e6 / sorted(v)[1], gbs=8 * npix * sorted(v)[1] / 1e9, runs_us=[1e6 / r for r in v],
+                          spread=(max(v) - min(v)) / sorted(v)[1]) for name, v in rates.items()}
+        row["buffer_sets"] = sets
+        row["composed_over_fused"] = row["composed"]["us"] / row["fused"]["us"]
+        out[f"{n}x{H}x{W}"] = row
+        del pred, gt, pl, gl
+        torch.cuda.empty_cache()
+    net = make_net().to(dev).eval()
+    frames = torch.randint(0, 256, (8, 2, 256, 512, 3), dtype=torch.uint8, device=dev)
+    labels = torch.randint(0, 20, (8, 2, 256, 512), dtype=torch.uint8, device=dev)
+    syn = VideoSynthesizer(net, max_batch=8)
+    fwd = lambda: syn.extrapolate(frames, labels, 1)  # noqa: E731
+    fwd()
+    fwd()
+    us = 1e6 / sorted(timed(fwd, seconds) for _ in range(3))[1]
+    out["forward_8x256x512_bf16_us"] = us
+    out["fused_8x256x512_over_forward"] = out["8x256x512"]["fused"]["us"] / us
+    out["composed_8x256x512_over_forward"] = out["8x256x512"]["composed"]["us"] / us
+    return out
+
+
 def module_rollout(net, frames, labels, steps):
     """the baseline: the rollout through the module forward plus torch glue (one-hot, cat, argmax,
     quantise), everything on the device; the prediction is the last stage's finest image, fed
@@ -253,7 +321,15 @@ def main():
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--interpolate-only", action="store_true")
     ap.add_argument("--two-stage", action="store_true", help="only the two-stage legs")
+    ap.add_argument("--score", action="store_true", help="only the held-out scoring legs")
     a = ap.parse_args()
+    if a.score:
+        res = dict(score=score_numbers(torch.device("cuda:0"), a.seconds))
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.two_stage:
         res = dict(two_stage_arena=two_stage_arena_numbers())
         if torch.cuda.is_available():
