@@ -137,6 +137,21 @@ class SynthFinishDesc(ctypes.Structure):
     ]
 
 
+class SynthLoadPadDesc(ctypes.Structure):
+    _fields_ = [
+        ("frames", vp), ("labels", vp), ("out", vp), ("label_out", vp),
+        ("n", i32), ("h", i32), ("w", i32), ("hp", i32), ("wp", i32), ("out_ld", i32),
+    ]
+
+
+class SynthFinishCropDesc(ctypes.Structure):
+    _fields_ = [
+        ("rgb", vp), ("seg", vp), ("frame", vp), ("label", vp), ("label_canvas", vp),
+        ("n", i32), ("h", i32), ("w", i32), ("hp", i32), ("wp", i32),
+        ("rgb_ld", i32), ("seg_ld", i32), ("n_classes", i32), ("pad0", i32),
+    ]
+
+
 class SynthBridgeDesc(ctypes.Structure):
     _fields_ = [
         ("rgb", vp), ("seg", vp), ("dst", vp), ("npix", i64),
@@ -258,7 +273,8 @@ class Op(ctypes.Structure):
 _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, OP_COLSUM: ColsumDesc,
         OP_EW: EwDesc, OP_LOSS: LossDesc, OP_PACK: PackDesc, OP_BN_FWD: BnDesc, OP_HEAD_FWD: HeadDesc,
         OP_ATTN: AttnDesc, OP_HEAD3_BWD: Head3BwdDesc, OP_SEGENC_FWD: SegencDesc, OP_SEGENC_BWD: SegencBwdDesc, OP_WREDUCE_MULTI: WreduceMultiDesc, 100: WarpDesc, 101: SoftmaxDesc, 102: SnLayer, 103: ClipDesc,
-        104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc, 107: SynthScoreDesc}
+        104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc, 107: SynthScoreDesc,
+        108: SynthLoadPadDesc, 109: SynthFinishCropDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -270,6 +286,7 @@ EXPORTS = [
     "dvie_adam_dev", "dvie_mfma_probe", "dvie_launch_probe", "dvie_sum_f32", "dvie_wgrad_bias_slabs", "dvie_head3_bwd",
     "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_pack_blocks", "dvie_trace_kernels", "dvie_traced_kernels",
     "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_score_ws_bytes",
+    "dvie_synth_load_pad", "dvie_synth_finish_crop",
 ]
 
 _lib = None
@@ -305,7 +322,7 @@ def load():
                      "dvie_loss", "dvie_warp_fwd", "dvie_warp_bwd", "dvie_bn_fwd", "dvie_bn_bwd", "dvie_head_fwd",
                      "dvie_head_bwd", "dvie_softmax_fwd", "dvie_softmax_bwd", "dvie_clip_prep", "dvie_attn",
                      "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
-                     "dvie_synth_bridge", "dvie_synth_score"):
+                     "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]

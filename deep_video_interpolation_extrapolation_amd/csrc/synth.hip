@@ -4,7 +4,9 @@
 //   dvie_synth_finish  the plan's fp32 rgb / segmentation-logit outputs -> uint8 frames and
 //                      uint8 label maps (clamp + quantise, argmax);
 //   dvie_synth_bridge  between two plans of a two-stage forward: an fp32 image and the coarse
-//                      logits -> [clamp(image) | softmax(logits)] in the next plan's input buffer.
+//                      logits -> [clamp(image) | softmax(logits)] in the next plan's input buffer;
+//   dvie_synth_load_pad / dvie_synth_finish_crop  load and finish for a frame of any size on a
+//                      padded canvas: the replicate padding and the crop happen in these launches.
 // They replace the eager glue of InterTrainer.mini_test (normalize, argmax, one_hot, cat and
 // the fp32 20-channel one-hot kept per frame).
 //
@@ -102,6 +104,83 @@ __global__ __launch_bounds__(256) void synth_finish_kernel(const dvie_synth_fini
       for (int c = 0; c < 3; ++c) p.frame[3 * pix + c] = (uint8_t)(rgb >> (8 * c));
     }
     if (p.label) p.label[pix] = (uint8_t)lab;
+  }
+}
+
+// The padded-canvas forms of load and finish (dvie.h).  Both launch one block row per canvas row
+// (blockIdx.x = image * hp + y, blockIdx.y = the 256-thread chunk of the row), so the canvas
+// coordinates cost one 32-bit division per thread and nothing is 64-bit but the addresses.
+//
+// load_pad: four output floats per thread as in load, a wave's stores one contiguous run of a
+// canvas row; the thread that owns a pixel's channels 0-3 also copies its label byte.
+__global__ __launch_bounds__(256) void synth_load_pad_kernel(const dvie_synth_load_pad_desc p, int ldq) {
+  const int e = blockIdx.y * 256 + threadIdx.x;
+  if (e >= p.wp * ldq) return;
+  const int x = e / ldq, q = e - x * ldq;
+  const int row = blockIdx.x, img = row / p.hp, y = row - img * p.hp;
+  const long long pix = (long long)row * p.wp + x;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (q == 0) {
+    const long long src = ((long long)img * p.h + min(y, p.h - 1)) * p.w + min(x, p.w - 1);
+    const uint8_t* s = p.frames + src * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = ((float)s[c] / 255.f - 0.5f) / 0.5f;  // = synth_load_kernel's, bit for bit
+    if (p.labels) p.label_out[pix] = p.labels[src];
+  }
+  *(f32x4*)(p.out + pix * p.out_ld + 4 * q) = v;
+}
+
+// finish_crop: one lane per CANVAS pixel, finish's loads.  wp % 4 == 0, so the four lanes of a
+// quad are four pixels of one canvas row and label_canvas keeps finish's dword stores
+// (kCanvasDword: label_canvas is 4-byte aligned).  The cropped outputs have rows of w * 3 and w
+// bytes at any alignment and are stored bytewise.  A pad pixel loads its logits only for
+// label_canvas and its rgb never.
+template <bool kCanvasDword>
+__global__ __launch_bounds__(256) void synth_finish_crop_kernel(const dvie_synth_finish_crop_desc p) {
+  const int x = blockIdx.y * 256 + threadIdx.x;
+  if (x >= p.wp) return;  // (whole quads: wp and 256 are multiples of 4)
+  const int row = blockIdx.x, img = row / p.hp, y = row - img * p.hp;
+  const bool inside = y < p.h && x < p.w;
+  if (!inside && !p.label_canvas) return;  // (no exchange follows without label_canvas)
+  const long long pix = (long long)row * p.wp + x;
+  uint32_t lab;
+  {  // = synth_finish_kernel's argmax, expression for expression
+    const float* s = p.seg + pix * p.seg_ld;
+    float best = -INFINITY;
+    int bi = 0;
+#pragma unroll 2
+    for (int c0 = 0; c0 < p.n_classes; c0 += 4) {
+      const f32x4 v = *(const f32x4*)(s + c0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (c0 + k < p.n_classes && v[k] > best) {
+          best = v[k];
+          bi = c0 + k;
+        }
+    }
+    lab = (uint32_t)bi;
+  }
+  if (p.label_canvas) {
+    if (kCanvasDword) {
+      const int j = threadIdx.x & 3;
+      uint32_t w = lab << (8 * j);
+      w |= __shfl_xor(w, 1);
+      w |= __shfl_xor(w, 2);
+      if (j == 0) *(uint32_t*)(p.label_canvas + pix) = w;
+    } else {
+      p.label_canvas[pix] = (uint8_t)lab;
+    }
+  }
+  if (inside) {
+    const long long o = ((long long)img * p.h + y) * p.w + x;
+    const f32x4 v = *(const f32x4*)(p.rgb + pix * p.rgb_ld);  // v[3] is padding: loaded, never used
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {  // = synth_finish_kernel's quantisation
+      const float t = fminf(fmaxf(v[c], -1.f), 1.f);
+      const float u = rintf(scale_unfused(t));
+      p.frame[3 * o + c] = (uint8_t)(int)u;
+    }
+    p.label[o] = (uint8_t)lab;
   }
 }
 
@@ -242,6 +321,46 @@ int dvie_synth_finish(const dvie_synth_finish_desc* d, void* stream) {
     DVIE_LAUNCH(synth_finish_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *d);
   else
     DVIE_LAUNCH(synth_finish_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *d);
+  DVIE_RETURN_LAUNCH();
+}
+
+int dvie_synth_load_pad(const dvie_synth_load_pad_desc* d, void* stream) {
+  DVIE_CHECK_ARG(d && d->frames && d->out, "synth_load_pad: frames / out must not be null");
+  DVIE_CHECK_ARG((d->labels != nullptr) == (d->label_out != nullptr),
+                 "synth_load_pad: labels and label_out must be given together");
+  DVIE_CHECK_ARG(d->n >= 1, "synth_load_pad: n=%d must be positive", d->n);
+  DVIE_CHECK_ARG(d->h >= 1 && d->h <= d->hp, "synth_load_pad: h=%d must be in 1..hp=%d", d->h, d->hp);
+  DVIE_CHECK_ARG(d->w >= 1 && d->w <= d->wp, "synth_load_pad: w=%d must be in 1..wp=%d", d->w, d->wp);
+  DVIE_CHECK_ARG(d->out_ld >= 4 && d->out_ld % 4 == 0 && (((uintptr_t)d->out) & 15) == 0,
+                 "synth_load_pad: out_ld=%d must be a multiple of 4 (>= 4) and out 16-byte aligned", d->out_ld);
+  const int ldq = d->out_ld / 4;
+  const long long rows = (long long)d->n * d->hp, chunks = ((long long)d->wp * ldq + 255) / 256;
+  DVIE_CHECK_ARG(rows < (1LL << 31) && chunks <= 65535, "synth_load_pad: grid too large");
+  DVIE_LAUNCH(synth_load_pad_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, *d, ldq);
+  DVIE_RETURN_LAUNCH();
+}
+
+int dvie_synth_finish_crop(const dvie_synth_finish_crop_desc* d, void* stream) {
+  DVIE_CHECK_ARG(d && d->rgb && d->seg && d->frame && d->label,
+                 "synth_finish_crop: rgb / seg / frame / label must not be null");
+  DVIE_CHECK_ARG(d->n >= 1, "synth_finish_crop: n=%d must be positive", d->n);
+  DVIE_CHECK_ARG(d->h >= 1 && d->h <= d->hp, "synth_finish_crop: h=%d must be in 1..hp=%d", d->h, d->hp);
+  DVIE_CHECK_ARG(d->w >= 1 && d->w <= d->wp, "synth_finish_crop: w=%d must be in 1..wp=%d", d->w, d->wp);
+  DVIE_CHECK_ARG(d->wp % 4 == 0, "synth_finish_crop: wp=%d must be a multiple of 4", d->wp);
+  DVIE_CHECK_ARG(d->rgb_ld % 4 == 0 && d->seg_ld % 4 == 0 && d->rgb_ld >= 4 && d->seg_ld >= 4,
+                 "synth_finish_crop: leading dimensions rgb_ld=%d seg_ld=%d must be multiples of 4 (>= 4)", d->rgb_ld,
+                 d->seg_ld);
+  DVIE_CHECK_ARG(((((uintptr_t)d->rgb) | ((uintptr_t)d->seg)) & 15) == 0,
+                 "synth_finish_crop: rgb / seg must be 16-byte aligned");
+  DVIE_CHECK_ARG(d->n_classes > 0 && d->n_classes <= d->seg_ld && d->n_classes <= 256,
+                 "synth_finish_crop: n_classes=%d must be in 1..min(seg_ld=%d, 256)", d->n_classes, d->seg_ld);
+  const long long rows = (long long)d->n * d->hp, chunks = ((long long)d->wp + 255) / 256;
+  DVIE_CHECK_ARG(rows < (1LL << 31) && chunks <= 65535, "synth_finish_crop: grid too large");
+  const dim3 grid((unsigned)rows, (unsigned)chunks);
+  if ((((uintptr_t)d->label_canvas) & 3) == 0)
+    DVIE_LAUNCH(synth_finish_crop_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *d);
+  else
+    DVIE_LAUNCH(synth_finish_crop_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *d);
   DVIE_RETURN_LAUNCH();
 }
 

@@ -790,6 +790,8 @@ size_t dvie_abi_sizeof(int which) {
     case 105: return sizeof(dvie_synth_finish_desc);
     case 106: return sizeof(dvie_synth_bridge_desc);
     case 107: return sizeof(dvie_synth_score_desc);
+    case 108: return sizeof(dvie_synth_load_pad_desc);
+    case 109: return sizeof(dvie_synth_finish_crop_desc);
     default: return 0;
   }
 }

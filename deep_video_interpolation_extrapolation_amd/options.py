@@ -16,6 +16,12 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
                             frames from a clip's first two and scores them against the frames that
                             follow.  Writes <cycgen_load_dir>/synth_eval/scores.json (per clip and slot
                             PSNR, SSIM, label accuracy, mIoU; the mean summary), no PNGs
+  --synth_pad {none,replicate}
+                            --split test: `none` takes only clips whose height and width are multiples
+                            of the net's coarsest stride (4; 8 with --highres_large; 4 << (--n_sc - 1)
+                            for the refinement stages); `replicate` takes any size: the clip is
+                            synthesised on a canvas rounded up to that multiple, its last row and
+                            column repeated, and the PNGs and scores have the clip's own size
 """
 import argparse
 
@@ -71,6 +77,7 @@ GLOBAL = [
     ("--clip_store", "clip_store", str, None, None),
     ("--synth_levels", "synth_levels", int, 1, None),
     ("--synth_eval", "synth_eval", bool, False, None),
+    ("--synth_pad", "synth_pad", str, "none", ["none", "replicate"]),
 ]
 
 # second-stage flags of the reference's INTER sub-command (options/options.py:296-380);

@@ -348,6 +348,22 @@ class InterTrainer:
                     save_image(lst[k].squeeze(0), os.path.join(d, names[k] + ".png"))
         return root
 
+    def _synthesizer(self):
+        """--split test: the VideoSynthesizer of this run (--bs pairs per forward, --synth_pad)"""
+        from ..synth import VideoSynthesizer
+        pad = getattr(self.args, "synth_pad", "none")
+        return VideoSynthesizer(self.model.module, max_batch=max(1, self.args.batch_size),
+                                pad=None if pad == "none" else pad)
+
+    def _on_clip(self, fn, syn, frames, labels, *rest):
+        """fn(syn, frames, labels, ...) of one clip; a frame size that --synth_pad none cannot run
+        is reported with the flag that can"""
+        from ..synth import FrameSizeError
+        try:
+            return fn(syn, frames, labels, *rest)
+        except FrameSizeError as e:
+            raise FrameSizeError(f"{e} (--synth_pad replicate takes clips of any size)") from None
+
     def _synthesize(self, syn, frames, labels):
         """--split test, interpolation: --synth_levels frame-rate doublings of the whole clip"""
         return syn.interpolate(frames, labels, levels=getattr(self.args, "synth_levels", 1))
@@ -360,14 +376,13 @@ class InterTrainer:
         label maps and their palette colouring, numbered in output order."""
         import numpy as np
         from PIL import Image
-        from ..synth import VideoSynthesizer
         from ..utils.net_utils import CITYSCAPES_COLORS
         a = self.args
         assert self.rank == 0, "test runs on one worker"
         assert a.cycgen_load_dir is not None, "please specify --cycgen_load_dir"
         if getattr(a, "synth_eval", False):
             return self.test_eval()
-        syn = VideoSynthesizer(self.model.module, max_batch=max(1, a.batch_size))
+        syn = self._synthesizer()
         img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
         root = os.path.join(a.cycgen_load_dir, "synth")
         palette = np.array(CITYSCAPES_COLORS, dtype=np.uint8)
@@ -376,8 +391,8 @@ class InterTrainer:
             assert len(names) >= 2, f"{clip}: a clip needs at least two frames"
             imgs = np.stack([np.asarray(Image.open(os.path.join(img_dir, clip, f)).convert("RGB")) for f in names])
             labs = np.stack([np.asarray(Image.open(os.path.join(seg_dir, clip, f)).convert("L")) for f in names])
-            frames, labels = self._synthesize(syn, torch.from_numpy(imgs)[None].to(self.device),
-                                              torch.from_numpy(labs)[None].to(self.device))
+            frames, labels = self._on_clip(self._synthesize, syn, torch.from_numpy(imgs)[None].to(self.device),
+                                           torch.from_numpy(labs)[None].to(self.device))
             frames, labels = frames[0].cpu().numpy(), labels[0].cpu().numpy()
             vis = palette[np.minimum(labels, len(palette) - 1)]  # (ids past the classes: "none")
             for sub, arr in (("rgb", frames), ("seg", labels), ("vis_seg", vis)):
@@ -409,9 +424,9 @@ class InterTrainer:
         goes to the log.  No PNG is written."""
         import numpy as np
         from PIL import Image
-        from ..synth import VideoSynthesizer, summarize
+        from ..synth import summarize
         a = self.args
-        syn = VideoSynthesizer(self.model.module, max_batch=max(1, a.batch_size))
+        syn = self._synthesizer()
         img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
         clips, cols = {}, [[] for _ in range(5)]
         for clip in sorted(d for d in os.listdir(img_dir) if os.path.isdir(os.path.join(img_dir, d))):
@@ -421,8 +436,8 @@ class InterTrainer:
                 continue
             imgs = np.stack([np.asarray(Image.open(os.path.join(img_dir, clip, f)).convert("RGB")) for f in names])
             labs = np.stack([np.asarray(Image.open(os.path.join(seg_dir, clip, f)).convert("L")) for f in names])
-            sc = self._score(syn, torch.from_numpy(imgs)[None].to(self.device), torch.from_numpy(labs)[None].to(self.device),
-                             clip)
+            sc = self._on_clip(self._score, syn, torch.from_numpy(imgs)[None].to(self.device),
+                               torch.from_numpy(labs)[None].to(self.device), clip)
             if sc is None:
                 continue
             vals = [v[0] for v in sc.host()]  # psnr, ssim, acc, miou of the one clip

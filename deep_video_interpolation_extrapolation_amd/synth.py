@@ -33,6 +33,13 @@ stays inside one triple runs on those views; where the clips of a triple do not 
 (a single video), a chunk spans several triples, whose frames are gathered into contiguous
 blocks first and whose outputs are scattered back (128 B per pixel and pair, against the
 several KB per pixel the forward itself moves).
+
+Frames of any size (pad="replicate"): the fp32 forms and the label maps the forwards read are
+canvases of canvas_size(H, W, multiple), the frame at the top-left.  `dvie_synth_load_pad`
+writes both canvases of an input slot (its last row and column repeated), and
+`dvie_synth_finish_crop` writes the cropped uint8 frame and label of a forward and, for a slot
+a later forward reads, the argmax over the whole canvas.  A prediction's pad region is the
+network's own output; the uint8 storage the caller gets stays (H, W).
 """
 import ctypes
 
@@ -115,6 +122,50 @@ def synth_finish(rgb=None, seg=None, frame=None, label=None, n_classes=20):
         d.seg, d.label, d.seg_ld, d.n_classes = seg.data_ptr(), label.data_ptr(), seg.shape[-1], n_classes
     d.npix = ref.numel() // ref.shape[-1]
     L.check(L.load().dvie_synth_finish(ctypes.byref(d), L.stream_ptr(ref.device)), "synth finish")
+
+
+def canvas_size(H, W, m):
+    """the padded canvas of an (H, W) frame: both rounded up to multiples of m"""
+    return -(-H // m) * m, -(-W // m) * m
+
+
+def synth_load_pad(frames, labels, out, label_out):
+    """uint8 frames (n, H, W, 3) and label maps (n, H, W) -> the fp32 canvas `out` (n, Hp, Wp, ld)
+    and the uint8 label canvas `label_out` (n, Hp, Wp), the last row and column repeated over the
+    pad region (dvie_synth_load_pad; all contiguous; labels and label_out both or neither None)."""
+    L.require_gpu(frames)
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 4 and frames.shape[-1] == 3
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] == frames.shape[0]
+    d = L.SynthLoadPadDesc()
+    d.frames, d.out = frames.data_ptr(), out.data_ptr()
+    d.n, d.h, d.w = frames.shape[:3]
+    d.hp, d.wp, d.out_ld = out.shape[1:]
+    if labels is not None or label_out is not None:
+        assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.shape == frames.shape[:3], labels.shape
+        assert label_out.dtype == torch.uint8 and label_out.is_contiguous() and label_out.shape == out.shape[:3]
+        d.labels, d.label_out = labels.data_ptr(), label_out.data_ptr()
+    L.check(L.load().dvie_synth_load_pad(ctypes.byref(d), L.stream_ptr(frames.device)), "synth load_pad")
+    return out
+
+
+def synth_finish_crop(rgb, seg, frame, label, label_canvas=None, n_classes=20):
+    """fp32 `rgb` (n, Hp, Wp, rgb_ld) and logits `seg` (n, Hp, Wp, seg_ld) over the canvas -> the
+    cropped uint8 `frame` (n, H, W, 3) and `label` (n, H, W) and, when given, the argmax of every
+    canvas pixel in `label_canvas` (n, Hp, Wp) (dvie_synth_finish_crop; all contiguous)."""
+    L.require_gpu(rgb)
+    assert rgb.dtype == torch.float32 and rgb.is_contiguous() and seg.dtype == torch.float32 and seg.is_contiguous()
+    assert rgb.dim() == 4 and rgb.shape[:3] == seg.shape[:3], (rgb.shape, seg.shape)
+    assert frame.dtype == torch.uint8 and frame.is_contiguous() and label.dtype == torch.uint8 and label.is_contiguous()
+    assert frame.dim() == 4 and frame.shape[0] == rgb.shape[0] and frame.shape[3] == 3 and label.shape == frame.shape[:3]
+    d = L.SynthFinishCropDesc()
+    d.rgb, d.seg, d.frame, d.label = rgb.data_ptr(), seg.data_ptr(), frame.data_ptr(), label.data_ptr()
+    d.n, d.h, d.w = frame.shape[:3]
+    d.hp, d.wp, d.rgb_ld = rgb.shape[1:]
+    d.seg_ld, d.n_classes = seg.shape[3], n_classes
+    if label_canvas is not None:
+        assert label_canvas.dtype == torch.uint8 and label_canvas.is_contiguous() and label_canvas.shape == rgb.shape[:3]
+        d.label_canvas = label_canvas.data_ptr()
+    L.check(L.load().dvie_synth_finish_crop(ctypes.byref(d), L.stream_ptr(rgb.device)), "synth finish_crop")
 
 
 class FrameScores:
@@ -267,21 +318,28 @@ class SynthScores:
         return summarize(pos.ravel(), psnr.ravel(), ssim.ravel(), acc.ravel(), miou.ravel())
 
 
+class FrameSizeError(ValueError):
+    """a frame size that VideoSynthesizer(pad=None) cannot run"""
+
+
 class _Captured:
     """One forward (every stage of it) + finish of a fixed (n, H, W) as a hipGraph over static
-    tensors."""
+    tensors.  With a padded canvas (H, W) is the canvas and `crop` the (h, w) of the frames that
+    leave: the static frame and label have the cropped size, and the label canvas is static too."""
 
-    def __init__(self, syn, n, H, W, dev):
+    def __init__(self, syn, n, H, W, dev, crop=None):
         f32, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
+        h, w = crop or (H, W)
         self.xa, self.xb = torch.zeros((n, H, W, 8), **f32), torch.zeros((n, H, W, 8), **f32)
         self.la, self.lb = torch.zeros((n, H, W), **u8), torch.zeros((n, H, W), **u8)
         self.rgb = torch.empty((n, H, W, 8), **f32)
-        self.frame, self.label = torch.empty((n, H, W, 3), **u8), torch.empty((n, H, W), **u8)
+        self.frame, self.label = torch.empty((n, h, w, 3), **u8), torch.empty((n, h, w), **u8)
+        self.lcan = torch.empty((n, H, W), **u8) if crop else None
         self.plans = syn._plans(n, H, W, dev)
         syn._scratch_of(n, H, W, dev)  # (allocated here, on the caller's stream, not in the warm-up)
         for p in self.plans:
             p.busy = True  # the graph holds these plans' pointers: nobody else gets them from the pool
-        args = (self.plans, self.xa, self.xb, self.la, self.lb, self.rgb, self.frame, self.label)
+        args = (self.plans, self.xa, self.xb, self.la, self.lb, self.rgb, self.frame, self.label, self.lcan)
         side = torch.cuda.Stream(dev)  # warm-up on a side stream, as stream capture requires
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -292,11 +350,12 @@ class _Captured:
         with torch.cuda.graph(self.graph):  # a single-stream chain: the forward list, then finish
             syn._run(*args)
 
-    def __call__(self, xa, xb, la, lb, rgb, frame, label):
+    def __call__(self, xa, xb, la, lb, rgb, frame, label, lcan=None):
         for dst, src in ((self.xa, xa), (self.xb, xb), (self.la, la), (self.lb, lb)):
             dst.copy_(src, non_blocking=True)
         self.graph.replay()
-        for dst, src in ((rgb, self.rgb), (frame, self.frame), (label, self.label)):
+        for dst, src in ((rgb, self.rgb), (frame, self.frame), (label, self.label)) + \
+                (((lcan, self.lcan),) if lcan is not None else ()):
             dst.copy_(src, non_blocking=True)
 
 
@@ -310,9 +369,16 @@ class VideoSynthesizer:
     returned and fed back is the last stage's finest image (module docstring); the label comes
     from the coarse logits.  GAN and VAE nets and a bare HRNet raise ValueError.  max_batch:
     frame pairs per forward.  graph: replay one captured hipGraph per forward (built per
-    (n, H, W) at first use; call reset() after the net's parameters were moved or replaced)."""
+    (n, H, W) at first use; call reset() after the net's parameters were moved or replaced).
+    pad: None -- H and W must be multiples of `multiple` (ValueError otherwise); "replicate" --
+    any H, W >= 1: the frames sit at the top-left of a canvas of canvas(H, W), whose other rows
+    and columns repeat an input frame's (and its label map's) last row and column.  The canvas
+    persists through the rollout: a prediction is the network's raw output over the whole canvas,
+    its label canvas the argmax over the whole canvas, and both feed later forwards as they are
+    (the pad region is not re-replicated).  What is returned is cropped to (H, W), so the result
+    equals padding the uint8 inputs, running pad=None on the canvas and cropping."""
 
-    def __init__(self, net, max_batch=8, graph=False):
+    def __init__(self, net, max_batch=8, graph=False, pad=None):
         from .nets.ExtraNet import ExtraNet, ExtraRefineNet, ExtraStage3Net
         from .nets.HRNet import HRNet
         from .nets.InterNet import InterNet
@@ -333,6 +399,9 @@ class VideoSynthesizer:
             raise ValueError("VideoSynthesizer needs one predicted frame from two (num_pred_once 1, no "
                              "fix_init_frames / inpaint_mask)")
         assert max_batch >= 1
+        if pad not in (None, "replicate"):
+            raise ValueError(f'pad must be None or "replicate", got {pad!r}')
+        self.pad = pad
         net.eval()
         self.net, self.cm, self.max_batch, self.graph = net, cm, int(max_batch), bool(graph)
         self._scratch = {}  # (n, H, W, device) -> the scratch tensors of a forward
@@ -344,6 +413,17 @@ class VideoSynthesizer:
             for p in c.plans:
                 p.busy = False
         self._graphs, self._scratch = {}, {}
+
+    @property
+    def multiple(self):
+        """what H and W of a forward must be multiples of: the net's coarsest stride (HRNet 4, 8
+        with highres_large; a refinement stage 4 << (n_scales - 1))"""
+        return max([8 if self.cm.highres_large else 4] + [4 << (s.n_scales - 1) for s in self.stages])
+
+    def canvas(self, H, W):
+        """(Hp, Wp) of the canvas an (H, W) frame is synthesised on when pad is "replicate": both
+        rounded up to `multiple`"""
+        return canvas_size(H, W, self.multiple)
 
     # ---------------- one forward ----------------
     def _plans(self, n, H, W, dev):
@@ -365,9 +445,10 @@ class VideoSynthesizer:
             self._scratch[key] = sc
         return self._scratch[key]
 
-    def _run(self, plans, xa, xb, la, lb, rgb, frame, label):
+    def _run(self, plans, xa, xb, la, lb, rgb, frame, label, lcan=None):
         """rgb (fp32, raw), frame, label <- net(xa, xb | la, lb); every tensor a contiguous
-        (n, H, W, ...) block (the inputs may be strided over n)."""
+        (n, H, W, ...) block (the inputs may be strided over n).  On a padded canvas frame and
+        label are (n, h, w, ...), the crop, and lcan (or None) gets the label canvas (n, H, W)."""
         n, H, W, _ = rgb.shape
         sc = self._scratch_of(n, H, W, rgb.device)
         seg = sc["seg"]
@@ -394,16 +475,20 @@ class VideoSynthesizer:
                 plan.set_input_labels("nseg", [la, lb])
                 plan.set_output_nchw("out", imgs[k + 1].permute(0, 3, 1, 2))
             plan.run_forward()
-        synth_finish(rgb, seg, frame, label, n_classes=self.cm.n_classes)
+        if frame.shape[1:3] == (H, W):
+            synth_finish(rgb, seg, frame, label, n_classes=self.cm.n_classes)
+        else:
+            synth_finish_crop(rgb, seg, frame, label, lcan, n_classes=self.cm.n_classes)
 
-    def _pair(self, xa, xb, la, lb, rgb, frame, label):
+    def _pair(self, xa, xb, la, lb, rgb, frame, label, lcan=None):
         n, H, W, _ = rgb.shape
         if not self.graph:
-            return self._run(self._plans(n, H, W, rgb.device), xa, xb, la, lb, rgb, frame, label)
-        key = (n, H, W, rgb.device)
+            return self._run(self._plans(n, H, W, rgb.device), xa, xb, la, lb, rgb, frame, label, lcan)
+        crop = tuple(frame.shape[1:3]) if frame.shape[1:3] != (H, W) else ()
+        key = (n, H, W, rgb.device) + crop
         if key not in self._graphs:
-            self._graphs[key] = _Captured(self, n, H, W, rgb.device)
-        self._graphs[key](xa, xb, la, lb, rgb, frame, label)
+            self._graphs[key] = _Captured(self, n, H, W, rgb.device, crop)
+        self._graphs[key](xa, xb, la, lb, rgb, frame, label, lcan)
 
     # ---------------- clips ----------------
     def _check(self, frames, labels):
@@ -412,9 +497,11 @@ class VideoSynthesizer:
                 or labels.shape != frames.shape[:4] or labels.device != frames.device:
             raise ValueError("frames: uint8 (B, T, H, W, 3), labels: uint8 (B, T, H, W), on one device; got "
                              f"{tuple(frames.shape)} {frames.dtype}, {tuple(labels.shape)} {labels.dtype}")
-        m = max([8 if self.cm.highres_large else 4] + [4 << (s.n_scales - 1) for s in self.stages])
-        if frames.shape[2] % m or frames.shape[3] % m:
-            raise ValueError(f"H and W must be multiples of {m}, got {tuple(frames.shape[2:4])}")
+        m = self.multiple
+        if self.pad is None and (frames.shape[2] % m or frames.shape[3] % m):
+            raise FrameSizeError(f"H and W must be multiples of {m}, got {tuple(frames.shape[2:4])}")
+        if frames.shape[2] < 1 or frames.shape[3] < 1:
+            raise ValueError(f"H and W must be at least 1, got {tuple(frames.shape[2:4])}")
 
     def chunks(self, triples, B):
         """The forwards of one level: its pairs (triple, clip), triples in order and the clips
@@ -439,39 +526,52 @@ class VideoSynthesizer:
     def _roll(self, frames, labels, n_slots, in_slots, levels, keep):
         """The slot-major state, the input frames placed and loaded, then the levels (lists of
         (left, right, out) triples) run in order.  keep(slot): a later forward reads the slot,
-        so its fp32 form is kept (other predictions go through one scratch block)."""
+        so its fp32 form is kept (other predictions go through one scratch block).  On a padded
+        canvas (pad="replicate", H or W no multiple) the fp32 forms are canvases, a kept slot
+        also keeps its label canvas, and the public fr / lb stay (H, W): load_pad fills both
+        canvases of an input slot, finish_crop writes the crop and the label canvas."""
         B, _, H, W, _ = frames.shape
         dev = frames.device
+        Hp, Wp = self.canvas(H, W) if self.pad else (H, W)
+        padded = (Hp, Wp) != (H, W)
+        u8 = dict(dtype=torch.uint8, device=dev)
         with torch.no_grad():
-            fr = torch.empty((n_slots, B, H, W, 3), dtype=torch.uint8, device=dev)
-            lb = torch.empty((n_slots, B, H, W), dtype=torch.uint8, device=dev)
+            fr = torch.empty((n_slots, B, H, W, 3), **u8)
+            lb = torch.empty((n_slots, B, H, W), **u8)
             for t, s in enumerate(in_slots):  # the originals pass through bit for bit
                 fr[s].copy_(frames[:, t])
                 lb[s].copy_(labels[:, t])
-            res = {s: torch.empty((B, H, W, 8), dtype=torch.float32, device=dev) for s in range(n_slots) if keep(s)}
-            tmp = torch.empty((self.max_batch, H, W, 8), dtype=torch.float32, device=dev)
-            tfr = tlb = None
+            res = {s: torch.empty((B, Hp, Wp, 8), dtype=torch.float32, device=dev) for s in range(n_slots) if keep(s)}
+            # lc[s]: the label map of slot s as a forward reads it -- lb[s] itself, or its canvas
+            lc = {s: torch.empty((B, Hp, Wp), **u8) for s in res} if padded else lb
+            tmp = torch.empty((self.max_batch, Hp, Wp, 8), dtype=torch.float32, device=dev)
+            tfr = tlb = tlc = None
             for s in in_slots:
                 if s in res:
-                    synth_load(fr[s], res[s])
+                    if padded:
+                        synth_load_pad(fr[s], lb[s], res[s], lc[s])
+                    else:
+                        synth_load(fr[s], res[s])
             for triples in levels:
                 for chunk in self.chunks(triples, B):
                     if len(chunk) == 1:  # one triple: its slots are contiguous blocks, used in place
                         a, b, o, b0, b1 = chunk[0]
                         rgb = res[o][b0:b1] if o in res else tmp[:b1 - b0]
-                        self._pair(res[a][b0:b1], res[b][b0:b1], lb[a, b0:b1], lb[b, b0:b1], rgb, fr[o, b0:b1],
-                                   lb[o, b0:b1])
+                        self._pair(res[a][b0:b1], res[b][b0:b1], lc[a][b0:b1], lc[b][b0:b1], rgb, fr[o, b0:b1],
+                                   lb[o, b0:b1], lc[o][b0:b1] if padded and o in res else None)
                         continue
                     # several triples: gather their frames, run one forward, scatter its outputs
                     n = sum(b1 - b0 for *_, b0, b1 in chunk)
                     if tfr is None:
-                        tfr = torch.empty((self.max_batch, H, W, 3), dtype=torch.uint8, device=dev)
-                        tlb = torch.empty((self.max_batch, H, W), dtype=torch.uint8, device=dev)
+                        tfr = torch.empty((self.max_batch, H, W, 3), **u8)
+                        tlb = torch.empty((self.max_batch, H, W), **u8)
+                        tlc = torch.empty((self.max_batch, Hp, Wp), **u8) if padded else None
                     xa = torch.cat([res[a][b0:b1] for a, _, _, b0, b1 in chunk])
                     xb = torch.cat([res[b][b0:b1] for _, b, _, b0, b1 in chunk])
-                    la = torch.cat([lb[a, b0:b1] for a, _, _, b0, b1 in chunk])
-                    lb2 = torch.cat([lb[b, b0:b1] for _, b, _, b0, b1 in chunk])
-                    self._pair(xa, xb, la, lb2, tmp[:n], tfr[:n], tlb[:n])
+                    la = torch.cat([lc[a][b0:b1] for a, _, _, b0, b1 in chunk])
+                    lb2 = torch.cat([lc[b][b0:b1] for _, b, _, b0, b1 in chunk])
+                    kept = padded and any(o in res for _, _, o, _, _ in chunk)
+                    self._pair(xa, xb, la, lb2, tmp[:n], tfr[:n], tlb[:n], tlc[:n] if kept else None)
                     k = 0
                     for _, _, o, b0, b1 in chunk:
                         m = b1 - b0
@@ -479,6 +579,8 @@ class VideoSynthesizer:
                         lb[o, b0:b1].copy_(tlb[k:k + m])
                         if o in res:
                             res[o][b0:b1].copy_(tmp[k:k + m])
+                            if padded:
+                                lc[o][b0:b1].copy_(tlc[k:k + m])
                         k += m
         return fr, lb
 

@@ -818,6 +818,50 @@ int dvie_synth_load(const dvie_synth_load_desc* d, void* stream);
 int dvie_synth_finish(const dvie_synth_finish_desc* d, void* stream);
 
 /*
+ * Frames of any size on a padded canvas (VideoSynthesizer(pad="replicate")).  The nets need
+ * H and W to be multiples of their coarsest stride; a frame (h, w) sits at the top-left of a
+ * canvas (hp, wp) >= (h, w) that the forwards run on, and only the two pointwise ends know the
+ * difference.
+ *
+ * dvie_synth_load_pad: uint8 frames (n, h, w, 3) and, optionally, uint8 label maps (n, h, w)
+ *   -> the fp32 canvas out (n, hp, wp, out_ld) and the uint8 label canvas label_out
+ *   (n, hp, wp), one launch.  Canvas pixel (y, x) reads source pixel (min(y, h-1), min(x, w-1)):
+ *   rows h..hp-1 and columns w..wp-1 repeat the last row and column (a label byte is repeated
+ *   whatever its value).  Channels 0-2 are dvie_synth_load's expression, bit for bit, channels
+ *   3 .. out_ld-1 are 0.  labels and label_out: both or neither.  out_ld % 4 == 0 (>= 4), out
+ *   16-byte aligned; no alignment of the uint8 tensors is assumed.
+ *
+ * dvie_synth_finish_crop: the fp32 outputs of a forward over the canvas, rgb (n, hp, wp, rgb_ld)
+ *   and seg (n, hp, wp, seg_ld) -> the cropped uint8 frame (n, h, w, 3) and label (n, h, w),
+ *   both contiguous, of any byte alignment, and, when label_canvas is not NULL, the argmax of
+ *   EVERY canvas pixel in label_canvas (n, hp, wp) (what a later forward reads as this frame's
+ *   label map).  Quantisation and argmax are dvie_synth_finish's, expression for expression.
+ *   rgb of the pad region never reaches a result, and with label_canvas == NULL neither do the
+ *   pad region's logits (they are not read).  wp % 4 == 0; otherwise dvie_synth_finish's rules.
+ */
+typedef struct dvie_synth_load_pad_desc {
+  const uint8_t* frames;
+  const uint8_t* labels;
+  float* out;
+  uint8_t* label_out;
+  int n, h, w, hp, wp, out_ld;
+} dvie_synth_load_pad_desc;
+
+typedef struct dvie_synth_finish_crop_desc {
+  const float* rgb;
+  const float* seg;
+  uint8_t* frame;
+  uint8_t* label;
+  uint8_t* label_canvas;
+  int n, h, w, hp, wp;
+  int rgb_ld, seg_ld, n_classes;
+  int pad0;
+} dvie_synth_finish_crop_desc;
+
+int dvie_synth_load_pad(const dvie_synth_load_pad_desc* d, void* stream);
+int dvie_synth_finish_crop(const dvie_synth_finish_crop_desc* d, void* stream);
+
+/*
  * dvie_synth_bridge: the hand-off between two plans of a two-stage inference forward (coarse
  * HRNet -> SRNRefine -> MSResAttnRefine).  Per pixel it reads an fp32 image (3 channels at
  * rgb + p*rgb_ld) and the 20 fp32 coarse segmentation logits (seg + p*seg_ld) and writes one
@@ -904,7 +948,7 @@ int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
- * synth_bridge, synth_score). */
+ * synth_bridge, synth_score, synth_load_pad, synth_finish_crop). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

@@ -20,7 +20,14 @@
   losses.SSIM, losses.PSNR and losses.IoU, one frame at a time), rotating over buffer sets
   that exceed the 256 MiB Infinity Cache, and next to one batch-8 forward.
 
-    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json] [--two-stage | --score]
+* the padded canvas (--pad): us per launch and GB/s of dvie_synth_load_pad / dvie_synth_finish_crop
+  against dvie_synth_load / dvie_synth_finish on the same canvas (8x256x512 from 253x509 frames,
+  1x1088x1920 from a 1080x1920 frame), rotating over buffer sets that exceed the Infinity Cache,
+  the legs alternating, three rounds; and frames/s of one ExtraStage3Net rollout (bf16, n_scales 3)
+  of a 1080x1920 clip with pad="replicate" against the aligned path on the same clip padded to
+  1088x1920 beforehand, alternating in one process, with the differing bytes of the two results.
+
+    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json] [--two-stage | --score | --pad]
 """
 import argparse
 import json
@@ -37,7 +44,8 @@ from deep_video_interpolation_extrapolation_amd import nets  # noqa: E402
 from deep_video_interpolation_extrapolation_amd.runners.InterTrainer import InterTrainer  # noqa: E402
 from deep_video_interpolation_extrapolation_amd import losses  # noqa: E402
 from deep_video_interpolation_extrapolation_amd.synth import (VideoSynthesizer, frame_scores, synth_bridge,  # noqa: E402
-                                                              synth_finish, synth_load)
+                                                              synth_finish, synth_finish_crop, synth_load,
+                                                              synth_load_pad)
 
 
 def make_net(large=False):
@@ -221,6 +229,91 @@ def score_numbers(dev, seconds):
     return out
 
 
+def _alternate(legs, seconds, scale=1.0, rounds=3):
+    """legs {name: fn}, warmed up, then timed alternating `rounds` times -> {name: calls/s * scale per
+    round}"""
+    for fn in legs.values():
+        fn()
+        fn()
+    rates = {name: [] for name in legs}
+    for _ in range(rounds):
+        for name, fn in legs.items():
+            rates[name].append(timed(fn, seconds) * scale)
+    return rates
+
+
+def pad_kernel_numbers(dev, seconds):
+    """load_pad / finish_crop against load / finish on the same canvas, rotating over buffer sets of
+    more than 2 GB in all (every launch streams from HBM).  GB/s are of algorithmic bytes: finish
+    128 + 4 B per canvas pixel; finish_crop 96 B of logits per canvas pixel it reads (all with
+    label_canvas, the frame's without), 32 + 4 B per frame pixel and 1 B per label_canvas pixel;
+    load 3 + 32 B per canvas pixel; load_pad 4 B per frame pixel read, 32 + 1 B per canvas pixel."""
+    out = {}
+    for n, H, W, Hp, Wp in ((8, 253, 509, 256, 512), (1, 1080, 1920, 1088, 1920)):
+        cpix, fpix = n * Hp * Wp, n * H * W
+        sets = -(-(2200 << 20) // (cpix * 132))
+        u8c = dict(dtype=torch.uint8, device=dev)
+        rgb = [torch.rand((n, Hp, Wp, 8), device=dev) * 2.4 - 1.2 for _ in range(sets)]
+        seg = [torch.randn((n, Hp, Wp, 24), device=dev) for _ in range(sets)]
+        frame_c = [torch.empty((n, Hp, Wp, 3), **u8c) for _ in range(sets)]
+        label_c = [torch.empty((n, Hp, Wp), **u8c) for _ in range(sets)]
+        frame = [torch.empty((n, H, W, 3), **u8c) for _ in range(sets)]
+        label = [torch.empty((n, H, W), **u8c) for _ in range(sets)]
+        in_c = [torch.randint(0, 256, (n, Hp, Wp, 3), **u8c) for _ in range(sets)]
+        in_f = [torch.randint(0, 256, (n, H, W, 3), **u8c) for _ in range(sets)]
+        in_l = [torch.randint(0, 20, (n, H, W), **u8c) for _ in range(sets)]
+        k = [0]
+
+        def rot(fn):
+            def run():
+                i = k[0] = (k[0] + 1) % sets
+                fn(i)
+            return run
+
+        legs = dict(finish=rot(lambda i: synth_finish(rgb[i], seg[i], frame_c[i], label_c[i])),
+                    finish_crop=rot(lambda i: synth_finish_crop(rgb[i], seg[i], frame[i], label[i])),
+                    finish_crop_canvas=rot(lambda i: synth_finish_crop(rgb[i], seg[i], frame[i], label[i], label_c[i])),
+                    load=rot(lambda i: synth_load(in_c[i], rgb[i])),
+                    load_pad=rot(lambda i: synth_load_pad(in_f[i], in_l[i], rgb[i], label_c[i])),
+                    load_pad_frames_only=rot(lambda i: synth_load_pad(in_f[i], None, rgb[i], None)))
+        nbytes = dict(finish=cpix * 132, finish_crop=fpix * 132, finish_crop_canvas=cpix * 97 + fpix * 36,
+                      load=cpix * 35, load_pad=fpix * 4 + cpix * 33, load_pad_frames_only=fpix * 3 + cpix * 32)
+        rates = _alternate(legs, seconds)
+        row = {name: dict(us=1e6 / sorted(v)[1], gbs=nbytes[name] * sorted(v)[1] / 1e9, runs_us=[1e6 / r for r in v],
+                          spread=(max(v) - min(v)) / sorted(v)[1]) for name, v in rates.items()}
+        row["buffer_sets"] = sets
+        out[f"{n}x{H}x{W} on {n}x{Hp}x{Wp}"] = row
+        del rgb, seg, frame_c, label_c, frame, label, in_c, in_f, in_l, legs
+        torch.cuda.empty_cache()
+    return out
+
+
+def pad_rollout_numbers(dev, seconds, steps):
+    """one ExtraStage3Net rollout (bf16, n_scales 3: multiples of 16) of a 1080x1920 clip: pad="replicate"
+    against the aligned path (pad=None, the path there was before) on the same clip padded to
+    1088x1920 with clamped indices beforehand; alternating, three rounds"""
+    H, W = 1080, 1920
+    net = make_two_stage(3).to(dev).eval()
+    frames = torch.randint(0, 256, (1, 2, H, W, 3), dtype=torch.uint8, device=dev)
+    labels = torch.randint(0, 20, (1, 2, H, W), dtype=torch.uint8, device=dev)
+    padded, aligned = VideoSynthesizer(net, max_batch=1, pad="replicate"), VideoSynthesizer(net, max_batch=1)
+    Hp, Wp = padded.canvas(H, W)
+    iy, ix = (torch.arange(c, device=dev).clamp(max=s - 1) for c, s in ((Hp, H), (Wp, W)))
+    frames_c = frames.index_select(2, iy).index_select(3, ix).contiguous()
+    labels_c = labels.index_select(2, iy).index_select(3, ix).contiguous()
+    legs = dict(aligned_on_canvas=lambda: aligned.extrapolate(frames_c, labels_c, steps),
+                pad_replicate=lambda: padded.extrapolate(frames, labels, steps))
+    rates = _alternate(legs, seconds, scale=steps)
+    want, got = legs["aligned_on_canvas"](), legs["pad_replicate"]()
+    row = {name: dict(frames_per_s=sorted(v)[1], runs=v, spread=(max(v) - min(v)) / sorted(v)[1])
+           for name, v in rates.items()}
+    row["canvas"] = [Hp, Wp]
+    row["differing_bytes_after_crop"] = dict(frames=int((want[0][:, :, :H, :W] != got[0]).sum()),
+                                             labels=int((want[1][:, :, :H, :W] != got[1]).sum()))
+    row["pad_over_aligned"] = row["pad_replicate"]["frames_per_s"] / row["aligned_on_canvas"]["frames_per_s"]
+    return row
+
+
 def module_rollout(net, frames, labels, steps):
     """the baseline: the rollout through the module forward plus torch glue (one-hot, cat, argmax,
     quantise), everything on the device; the prediction is the last stage's finest image, fed
@@ -322,7 +415,17 @@ def main():
     ap.add_argument("--interpolate-only", action="store_true")
     ap.add_argument("--two-stage", action="store_true", help="only the two-stage legs")
     ap.add_argument("--score", action="store_true", help="only the held-out scoring legs")
+    ap.add_argument("--pad", action="store_true", help="only the padded-canvas legs")
     a = ap.parse_args()
+    if a.pad:
+        dev = torch.device("cuda:0")
+        res = dict(pad_kernels=pad_kernel_numbers(dev, a.seconds),
+                   pad_rollout_stage3_bf16_1080x1920=pad_rollout_numbers(dev, a.seconds, a.steps))
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.score:
         res = dict(score=score_numbers(torch.device("cuda:0"), a.seconds))
         print(json.dumps(res, indent=1))
