@@ -19,8 +19,8 @@ All activations are NHWC buffers allocated once per (batch, height, width) plan;
 kernels never allocate.  Reference semantics: nets/HRNet.py, nets/vgg.py, losses.py.
 """
 import ctypes
-import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -57,6 +57,18 @@ def _reduce_meta(name, r):
                 bytes=float(4 * (r.splits * rows * r.ws_k + out * (1 + r.beta))))
 
 
+class Epilogue(NamedTuple):
+    """What the kernel of a gradient contribution does on its way out (Plan._flush decides;
+    the fields are the keyword arguments of conv_desc / ew_desc / attn_desc): y = dact(z) *
+    (beta * y + kernel + res)."""
+    beta: int = 0  # 0: overwrite the gradient buffer, 1: accumulate into it
+    res: Optional[int] = None  # identity contribution added on the way (pointer, pixel stride)
+    res_ld: int = 0
+    dact: int = 0  # producer's activation derivative, from its output z
+    z: Optional[int] = None
+    z_ld: int = 0
+
+
 def rup(x, m):
     return (x + m - 1) // m * m
 
@@ -75,6 +87,7 @@ class Buffer:
     def __init__(self, name, H, W, C, dtype=None, external=False):
         self.name, self.H, self.W, self.C = name, H, W, C
         self.dtype = dtype  # None -> graph compute dtype
+        self.dt = None  # the plan's storage dtype
         self.external = external
         self.t = None  # forward storage
         self.g = None  # gradient storage [Nb, H, W, C] (compute dtype)
@@ -83,6 +96,9 @@ class Buffer:
         self.consumers = []  # (op, region)
         self.expected = {}  # read region key -> number of gradient contributions
         self.pending = {}  # read region key -> contributions recorded so far
+        self.n_flushed = 0  # regions whose gradient is complete
+        self.done = False  # every region's gradient is complete
+        self.dact_done = False  # ... and already the producer's pre-activation gradient
 
     def __repr__(self):
         return f"Buffer({self.name},{self.H}x{self.W}x{self.C})"
@@ -143,8 +159,11 @@ class ConvLayer:
         self.cmap = None  # packed input position -> source input channel (or -1)
         self.cin_p = None  # packed input channels
         self.cout_p = rup(self.cout, PADC)
+        self.kpad = None  # row length of the packed forward weights
         self.wf = None  # packed forward weights
+        self.cmap_t = None  # cmap on the device
         self.wd = []  # per dgrad phase: (tensor, taps(dict))
+        self.wd4 = None  # (tensor, kpad) of the one-launch stride-2 data gradient
         self.bias_p = None
         self.uses = 0
 
@@ -418,6 +437,9 @@ class Graph:
         self.layers = []
         self.outputs = {}
         self.caller_written = {}  # key -> region the caller writes before run_forward (Graph.caller_input)
+        self.heads = {}  # key -> region a HeadOp pools
+        self.segenc = []  # ConvOp triples marked by segenc_chain
+        self.bn_training = True  # owners set it to their module's training flag
         self.n_l1 = 0
 
     # ---------------- builder ----------------
@@ -555,7 +577,6 @@ class Graph:
     def head(self, x, pool, key):
         assert x.H >= pool and x.W >= pool
         self._add(HeadOp(x, pool, key))
-        self.heads = getattr(self, "heads", {})
         self.heads[key] = x
         return key
 
@@ -572,7 +593,7 @@ class Graph:
         """mark three ConvOps as HRNet's segmentation encoder (conv + ELU, conv + ELU, conv):
         the plan runs their forward as one dvie_segenc_fwd launch where the shapes allow
         (Plan._segenc_fwd); their backward is unchanged."""
-        self.__dict__.setdefault("segenc", []).append(tuple(ops))
+        self.segenc.append(tuple(ops))
 
     def _add(self, op):
         self.ops.append(op)
@@ -621,7 +642,7 @@ def forward_launches(g, nf):
     where they run as one fused launch."""
     fused_first, skip = {}, set()
     if os.environ.get("DVIE_SEGENC_FWD", "1") == "1":
-        for chain in getattr(g, "segenc", []):
+        for chain in g.segenc:
             if segenc_fusable(g.dtype, nf, chain):
                 fused_first[id(chain[0])] = chain
                 skip.update(id(op) for op in chain[1:])
@@ -631,7 +652,7 @@ def forward_launches(g, nf):
 def _op_regions(op):
     """every region an op reads or writes"""
     rs = list(op.inputs())
-    for r in (getattr(op, "out", None), getattr(op, "region", None)):  # (region: OutNCHWOp's source)
+    for r in (op.out, getattr(op, "region", None)):  # (region: OutNCHWOp's source)
         if r is not None:
             rs.append(r)
     return rs
@@ -648,7 +669,7 @@ def forward_lifetimes(g, nf):
             for r in _op_regions(op):
                 a, b = life.get(id(r.buf), (i, i))
                 life[id(r.buf)] = (min(a, i), max(b, i))
-    for r in getattr(g, "caller_written", {}).values():  # written before launch 0
+    for r in g.caller_written.values():  # written before launch 0
         life[id(r.buf)] = (0, life.get(id(r.buf), (0, 0))[1])
     return life
 
@@ -714,17 +735,35 @@ class Plan:
         self.busy = False
         self.generation = 0
         self.static_weights = False  # set by owners whose weights never train (nets/vgg.py)
-        self._pack_srcs, self._pack_sig = [], None
-        self._alloc()
+        self._pack_srcs, self._pack_sig, self._pack_descs = [], None, []
+        self.arena, self.arena_bytes, self.unaliased_bytes = None, None, 0  # (alias=True: one allocation)
+        self.l1_out = self.bn_partial = None  # feature-L1 values; BatchNorm partial sums
+        self.bn_splits = 1
+        self._seg_bwd, self._seg_inner = {}, set()  # fused seg-encoder backwards, their hidden maps
         self.fwd = []
         self.bwd = []
+        self.fwd_arr = self.bwd_arr = None  # the lists as the C arrays dvie_run_ops takes
+        self.fwd_off = self.n_bwd = 0
         self._l1_fwd = []  # (forward list index, level) of the VGG feature-L1 loss ops
+        self._l1_bwd = []  # (backward index, seed scale) of their gradient seeds
         self.ext_in = {}  # key -> list of (op index, InputOp) for patching
         self.ext_out = {}
+        self.ext_mask = {}  # key -> list of ('fwd'|'bwd', op index, MaskOp)
+        self.ext_nchw_out = {}  # key -> fwd op index of the NCHW sink
+        self.ext_head = {}  # key -> (fwd op index, rows)
+        self.ext_head_grad = {}  # key -> bwd op index
+        self.keep_grad = None  # the head gradient last handed to set_head_grad
         self.ext_grad = {}  # key -> list of bwd op indices (TONCHW)
         self._grad_slots = []  # (bwd index, layer, 'weight'|'bias', first use)
         self.ext_ograd = {}  # output key -> bwd op index of its gradient pack
+        self.wg_first = {}  # layer (or BatchNorm module) -> its gradient has a first writer
+        self._uses_left = {}  # trainable layer -> uses whose weight gradient is still to come
+        self.completions = []  # (bwd index, layer): the layer's parameter gradients are final
+        self._multi = []  # batched reductions: (host descriptor array, [(ws_ptr or None, float offset in self.ws)])
+        self._i2c = None  # im2col scratch shared by the layers that take that lowering
+        self.ws = None  # workspace of the weight-gradient / column-sum partials
         self.ws_floats = 1
+        self._alloc()
         self._build_pack()
         self._build_forward()
         if backward:
@@ -783,11 +822,10 @@ class Plan:
             for b in g.buffers:
                 if b.needs_grad and id(b) not in self._seg_inner:
                     b.g = torch.zeros((self.nb, b.H, b.W, b.C), dtype=self.dtype, device=self.device)
-            for b in g.buffers:
-                b.expected = {}
-                b.pending = {}
+            for b in g.buffers:  # (a graph compiled again starts its gradient bookkeeping over)
+                b.expected, b.pending = {}, {}
                 b.n_flushed = 0
-                b.done = False
+                b.done = b.dact_done = False
             for op in g.ops:
                 if isinstance(op, FuseOp) and op.detach:
                     continue
@@ -803,7 +841,6 @@ class Plan:
                     assert a0 + ac <= b0, f"{b}: consumers read overlapping regions {keys}"
         self.l1_out = torch.zeros(max(1, g.n_l1), dtype=torch.float32, device=self.device)
         self.keep.append(self.l1_out)
-        self.bn_splits = 1
         for op in g.ops:
             if isinstance(op, BNOp):
                 d = L.BnDesc()
@@ -903,7 +940,7 @@ class Plan:
         """packed [4 * cin_p][kpad] weights of the one-launch stride-2 data gradient: row block
         q = phase (a, b) = PH4_ORDER[q], tap (i, j) of the 2 x 2 grid = forward weight
         (kh, kw) = (a + 1 - 2i, b + 1 - 2j) (zero where that is outside the kernel)"""
-        if getattr(lay, "wd4", None) is not None:
+        if lay.wd4 is not None:
             return lay.wd4
         kpad = rup(4 * lay.cout_p, 64)
         t = torch.zeros((4 * lay.cin_p, kpad), dtype=self.dtype, device=self.device)
@@ -919,6 +956,13 @@ class Plan:
     def _op(self, kind):
         o = L.Op()
         o.kind = kind
+        # (o.meta, the profiling dict(cls, name, flops, bytes), exists only on the ops given one)
+        # where a weight-lane op's slabs live, in floats from the start of self.ws (resolved
+        # to pointers in _finalize): ws_base the writer's region (_batch_reductions), ws_off
+        # a reduction's offset inside it, bws_off a weight gradient's bias partials; ws_ptr: a
+        # reduction reading its site's own buffer instead
+        o.ws_base, o.ws_off, o.bws_off, o.ws_ptr = 0, 0, None, None
+        o.l1_seed = None  # a feature-L1 gradient seed: its scale before set_l1_loss's grad_scale
         return o
 
     def conv_desc(self, x_ptr, x_ld, n, ih, iw, c, w_ptr, kpad, cout, oh, ow, sy, sx, taps, y_ptr, y_ld, yh, yw,
@@ -967,9 +1011,6 @@ class Plan:
         return (0 if part == 0 else self.nf // 2), self.nf // 2
 
     # ---------------- forward ----------------
-    def _segenc_fusable(self, ops):
-        return segenc_fusable(self.dtype, self.nf, ops)
-
     def _segenc_fwd(self, ops):
         o0, o1, o2 = ops
         x, nf = o0.x, self.nf
@@ -988,134 +1029,137 @@ class Plan:
         return o
 
     def _build_forward(self):
-        g = self.g
-        nf = self.nf
         # the fused forward (one dvie_segenc_fwd per encoder) is the default since its stages
         # run two 32-pixel blocks per wave: 0.316 vs 0.344 ms per step for the three convs at
         # 8x256x512 (profiles/r06/segenc_*); DVIE_SEGENC_FWD=0 runs the three convs
-        for site in forward_launches(g, nf):
-            op = site[0]
+        for site in forward_launches(self.g, self.nf):
             if len(site) > 1:
                 self.fwd.append(self._segenc_fwd(tuple(site)))
                 continue
-            if isinstance(op, LabelInputOp):
-                o = self.ew_desc(L.EW_LABELS, nf, op.out.H, op.out.W, op.out.c, self.ptr(op.out), op.out.buf.C)
-                o.u.ew.ext_c = op.ext_c
-                self.ext_in.setdefault(op.key, []).append((len(self.fwd), op))
-                self.fwd.append(o)
-            elif isinstance(op, InputOp):
-                n0, cnt = self._part(op.part)
-                o = self.ew_desc(L.EW_NCHW, cnt, op.out.H, op.out.W, op.out.c, self.ptr(op.out, n0), op.out.buf.C)
-                o.u.ew.ext_c = op.ext_c
-                if op.normalize:
-                    m = torch.tensor(_IMAGENET_MEAN + [0.0] * 5, dtype=torch.float32, device=self.device)
-                    s = torch.tensor(_IMAGENET_STD + [1.0] * 5, dtype=torch.float32, device=self.device)
-                    self.keep += [m, s]
-                    o.u.ew.mean, o.u.ew.std = m.data_ptr(), s.data_ptr()
-                    op.std_t = s
-                self.ext_in.setdefault(op.key, []).append((len(self.fwd), op))
-                self.fwd.append(o)
-            elif isinstance(op, ConvOp):
-                lay, x, out = op.layer, op.x, op.out
-                ext = out.buf.external
-                o = self.conv_desc(
-                    self.ptr(x), x.buf.C, nf, x.H, x.W, x.c, lay.wf.data_ptr(), lay.kpad, lay.cout_p, out.H, out.W,
-                    lay.stride, lay.stride, lay.fwd_taps(), 0 if ext else self.ptr(out), out.buf.C, out.H, out.W,
-                    bias=lay.bias_p.data_ptr() if lay.has_bias else None,
-                    res=self.ptr(op.res) if op.res is not None else None,
-                    res_ld=op.res.buf.C if op.res is not None else 0, act=op.act,
-                    out_f32=(out.buf.dt == torch.float32 and self.dtype != torch.float32))
-                npx = nf * out.H * out.W
-                o.meta = dict(cls="conv_fwd", name=lay.name,
-                              flops=2.0 * npx * lay.cout * lay.cin * lay.kh * lay.kw,
-                              bytes=float(self.es * (nf * x.H * x.W * lay.cin + npx * lay.cout * (2 if op.res is not None else 1)
-                                                     + lay.cout * lay.cin * lay.kh * lay.kw)))
-                if ext:
-                    self.ext_out.setdefault(out.buf.name, []).append((len(self.fwd), out))
-                self.fwd.append(o)
-            elif isinstance(op, ConvTOp):
-                # the stride phases of the virtual conv's data gradient, over the ConvT input
-                lay, x, out = op.layer, op.x, op.out
-                assert not out.buf.external
-                for ph, wt, kpad in self._dgrad_weights(lay, out.H, out.W):
-                    o = self.conv_desc(
-                        self.ptr(x), x.buf.C, nf, x.H, x.W, lay.cout_p, wt.data_ptr(), kpad, out.c, ph["oh"], ph["ow"],
-                        1, 1, ph, self.ptr(out), out.buf.C, out.H, out.W, osy=lay.stride, osx=lay.stride,
-                        ory=ph["ry"], orx=ph["rx"], bias=lay.bias_p.data_ptr() if lay.has_bias else None, act=op.act,
-                        out_f32=(out.buf.dt == torch.float32 and self.dtype != torch.float32))
-                    npx = nf * ph["oh"] * ph["ow"]
-                    o.meta = dict(cls="conv_fwd", name=lay.name, flops=2.0 * npx * lay.cout * lay.cin * ph["th"] * ph["tw"],
-                                  bytes=float(self.es * (nf * x.H * x.W * lay.cout + npx * lay.cin)))
-                    self.fwd.append(o)
-            elif isinstance(op, AttnOp):
-                self.fwd.append(self._attn_fwd(op))
-            elif isinstance(op, FuseOp):
-                out = op.out
-                srcs = [(self.ptr(s), s.buf.C, s.H, s.W) for s in op.srcs]
-                o = self.ew_desc(L.EW_FUSE, nf, out.H, out.W, out.c, self.ptr(out), out.buf.C, srcs, act=op.act)
-                o.u.ew.align = int(op.align)
-                self.fwd.append(o)
-            elif isinstance(op, MaskOp):
-                out, src = op.out, op.src
-                o = self.ew_desc(L.EW_MASK, nf, out.H, out.W, out.c, self.ptr(out), out.buf.C,
-                                 [(self.ptr(src), src.buf.C, src.H, src.W)])
-                o.u.ew.ext_c = int(op.inverse)
-                self.ext_mask = getattr(self, "ext_mask", {})
-                self.ext_mask.setdefault(op.key, []).append(("fwd", len(self.fwd), op))
-                self.fwd.append(o)
-            elif isinstance(op, OutNCHWOp):
-                r = op.region
-                o = self.ew_desc(L.EW_TONCHW, nf, r.H, r.W, r.c, 0, 0, [(self.ptr(r), r.buf.C, r.H, r.W)])
-                o.u.ew.ext_c = op.channels
-                if op.clamp:
-                    o.u.ew.align, o.u.ew.scale = 1, float(op.clamp)
-                self.ext_nchw_out = getattr(self, "ext_nchw_out", {})
-                self.ext_nchw_out[op.key] = len(self.fwd)
-                self.fwd.append(o)
-            elif isinstance(op, PoolOp):
-                x, out = op.x, op.out
-                self.fwd.append(self.ew_desc(L.EW_POOL, nf, out.H, out.W, out.c, self.ptr(out), out.buf.C,
-                                             [(self.ptr(x), x.buf.C, x.H, x.W)]))
-            elif isinstance(op, BNOp):
-                o = self._op(L.OP_BN_FWD)
-                self._bn_common(o.u.bn, op, nf)
-                o.u.bn.y, o.u.bn.y_ld = self.ptr(op.out), op.out.buf.C
-                op.fwd_index = len(self.fwd)
-                self.bn_ops = getattr(self, "bn_ops", []) + [op]
-                self.fwd.append(o)
-            elif isinstance(op, HeadOp):
-                x = op.x
-                o = self._op(L.OP_HEAD_FWD)
-                d = o.u.head
-                d.x, d.x_ld = self.ptr(x), x.buf.C
-                d.n, d.h, d.w, d.c, d.pool, d.dtype = nf, x.H, x.W, x.c, op.pool, self.dt
-                rows = nf * (x.H // op.pool) * (x.W // op.pool)
-                op.pooled = torch.zeros(rows * x.c, dtype=torch.float32, device=self.device)
-                self.keep.append(op.pooled)
-                d.pooled = op.pooled.data_ptr()
-                self.ext_head = getattr(self, "ext_head", {})
-                self.ext_head[op.key] = (len(self.fwd), rows)
-                self.fwd.append(o)
-            elif isinstance(op, L1FeatOp):
-                a = op.a
-                half = nf // 2
-                o = self._op(L.OP_LOSS)
-                d = o.u.loss
-                d.a, d.b = self.ptr(a, 0), self.ptr(a, half)
-                sn, sh, sw = a.H * a.W * a.buf.C, a.W * a.buf.C, a.buf.C
-                d.a_sn, d.a_sc, d.a_sh, d.a_sw = sn, 1, sh, sw
-                d.b_sn, d.b_sc, d.b_sh, d.b_sw = sn, 1, sh, sw
-                d.kind, d.bsz, d.ch, d.h, d.w, d.dtype = L.LOSS_L1NHWC, half, a.c, a.H, a.W, self.dt
-                d.weight, d.out_scale = 1.0, 1.0
-                npart = L.load().dvie_loss_partial_count(ctypes.byref(d))
-                part = torch.zeros(max(1, npart), dtype=torch.float64, device=self.device)
-                self.keep.append(part)
-                d.partial = part.data_ptr()
-                d.out = self.l1_out.data_ptr() + 4 * op.idx
-                self._l1_fwd.append((len(self.fwd), op.idx))
-                self.fwd.append(o)
-            else:
-                raise TypeError(op)
+            lower = self._FWD.get(type(site[0]))
+            if lower is None:
+                raise TypeError(site[0])
+            lower(self, site[0])
+
+    def _label_input_fwd(self, op):
+        o = self.ew_desc(L.EW_LABELS, self.nf, op.out.H, op.out.W, op.out.c, self.ptr(op.out), op.out.buf.C)
+        o.u.ew.ext_c = op.ext_c
+        self.ext_in.setdefault(op.key, []).append((len(self.fwd), op))
+        self.fwd.append(o)
+
+    def _input_fwd(self, op):
+        n0, cnt = self._part(op.part)
+        o = self.ew_desc(L.EW_NCHW, cnt, op.out.H, op.out.W, op.out.c, self.ptr(op.out, n0), op.out.buf.C)
+        o.u.ew.ext_c = op.ext_c
+        if op.normalize:
+            m = torch.tensor(_IMAGENET_MEAN + [0.0] * 5, dtype=torch.float32, device=self.device)
+            s = torch.tensor(_IMAGENET_STD + [1.0] * 5, dtype=torch.float32, device=self.device)
+            self.keep += [m, s]
+            o.u.ew.mean, o.u.ew.std = m.data_ptr(), s.data_ptr()
+            op.std_t = s
+        self.ext_in.setdefault(op.key, []).append((len(self.fwd), op))
+        self.fwd.append(o)
+
+    def _conv_fwd(self, op):
+        lay, x, out, nf = op.layer, op.x, op.out, self.nf
+        ext = out.buf.external
+        o = self.conv_desc(
+            self.ptr(x), x.buf.C, nf, x.H, x.W, x.c, lay.wf.data_ptr(), lay.kpad, lay.cout_p, out.H, out.W,
+            lay.stride, lay.stride, lay.fwd_taps(), 0 if ext else self.ptr(out), out.buf.C, out.H, out.W,
+            bias=lay.bias_p.data_ptr() if lay.has_bias else None,
+            res=self.ptr(op.res) if op.res is not None else None,
+            res_ld=op.res.buf.C if op.res is not None else 0, act=op.act,
+            out_f32=(out.buf.dt == torch.float32 and self.dtype != torch.float32))
+        npx = nf * out.H * out.W
+        o.meta = dict(cls="conv_fwd", name=lay.name,
+                      flops=2.0 * npx * lay.cout * lay.cin * lay.kh * lay.kw,
+                      bytes=float(self.es * (nf * x.H * x.W * lay.cin + npx * lay.cout * (2 if op.res is not None else 1)
+                                             + lay.cout * lay.cin * lay.kh * lay.kw)))
+        if ext:
+            self.ext_out.setdefault(out.buf.name, []).append((len(self.fwd), out))
+        self.fwd.append(o)
+
+    def _convT_fwd(self, op):
+        # the stride phases of the virtual conv's data gradient, over the ConvT input
+        lay, x, out, nf = op.layer, op.x, op.out, self.nf
+        assert not out.buf.external
+        for ph, wt, kpad in self._dgrad_weights(lay, out.H, out.W):
+            o = self.conv_desc(
+                self.ptr(x), x.buf.C, nf, x.H, x.W, lay.cout_p, wt.data_ptr(), kpad, out.c, ph["oh"], ph["ow"],
+                1, 1, ph, self.ptr(out), out.buf.C, out.H, out.W, osy=lay.stride, osx=lay.stride,
+                ory=ph["ry"], orx=ph["rx"], bias=lay.bias_p.data_ptr() if lay.has_bias else None, act=op.act,
+                out_f32=(out.buf.dt == torch.float32 and self.dtype != torch.float32))
+            npx = nf * ph["oh"] * ph["ow"]
+            o.meta = dict(cls="conv_fwd", name=lay.name, flops=2.0 * npx * lay.cout * lay.cin * ph["th"] * ph["tw"],
+                          bytes=float(self.es * (nf * x.H * x.W * lay.cout + npx * lay.cin)))
+            self.fwd.append(o)
+
+    def _fuse_fwd(self, op):
+        out = op.out
+        srcs = [(self.ptr(s), s.buf.C, s.H, s.W) for s in op.srcs]
+        o = self.ew_desc(L.EW_FUSE, self.nf, out.H, out.W, out.c, self.ptr(out), out.buf.C, srcs, act=op.act)
+        o.u.ew.align = int(op.align)
+        self.fwd.append(o)
+
+    def _mask_fwd(self, op):
+        out, src = op.out, op.src
+        o = self.ew_desc(L.EW_MASK, self.nf, out.H, out.W, out.c, self.ptr(out), out.buf.C,
+                         [(self.ptr(src), src.buf.C, src.H, src.W)])
+        o.u.ew.ext_c = int(op.inverse)
+        self.ext_mask.setdefault(op.key, []).append(("fwd", len(self.fwd), op))
+        self.fwd.append(o)
+
+    def _out_nchw_fwd(self, op):
+        r = op.region
+        o = self.ew_desc(L.EW_TONCHW, self.nf, r.H, r.W, r.c, 0, 0, [(self.ptr(r), r.buf.C, r.H, r.W)])
+        o.u.ew.ext_c = op.channels
+        if op.clamp:
+            o.u.ew.align, o.u.ew.scale = 1, float(op.clamp)
+        self.ext_nchw_out[op.key] = len(self.fwd)
+        self.fwd.append(o)
+
+    def _pool_fwd(self, op):
+        x, out = op.x, op.out
+        self.fwd.append(self.ew_desc(L.EW_POOL, self.nf, out.H, out.W, out.c, self.ptr(out), out.buf.C,
+                                     [(self.ptr(x), x.buf.C, x.H, x.W)]))
+
+    def _bn_fwd(self, op):
+        o = self._op(L.OP_BN_FWD)
+        self._bn_common(o.u.bn, op, self.nf)
+        o.u.bn.y, o.u.bn.y_ld = self.ptr(op.out), op.out.buf.C
+        self.fwd.append(o)
+
+    def _head_fwd(self, op):
+        x = op.x
+        o = self._op(L.OP_HEAD_FWD)
+        d = o.u.head
+        d.x, d.x_ld = self.ptr(x), x.buf.C
+        d.n, d.h, d.w, d.c, d.pool, d.dtype = self.nf, x.H, x.W, x.c, op.pool, self.dt
+        rows = self.nf * (x.H // op.pool) * (x.W // op.pool)
+        op.pooled = torch.zeros(rows * x.c, dtype=torch.float32, device=self.device)
+        self.keep.append(op.pooled)
+        d.pooled = op.pooled.data_ptr()
+        self.ext_head[op.key] = (len(self.fwd), rows)
+        self.fwd.append(o)
+
+    def _l1feat_fwd(self, op):
+        a = op.a
+        half = self.nf // 2
+        o = self._op(L.OP_LOSS)
+        d = o.u.loss
+        d.a, d.b = self.ptr(a, 0), self.ptr(a, half)
+        sn, sh, sw = a.H * a.W * a.buf.C, a.W * a.buf.C, a.buf.C
+        d.a_sn, d.a_sc, d.a_sh, d.a_sw = sn, 1, sh, sw
+        d.b_sn, d.b_sc, d.b_sh, d.b_sw = sn, 1, sh, sw
+        d.kind, d.bsz, d.ch, d.h, d.w, d.dtype = L.LOSS_L1NHWC, half, a.c, a.H, a.W, self.dt
+        d.weight, d.out_scale = 1.0, 1.0
+        npart = L.load().dvie_loss_partial_count(ctypes.byref(d))
+        part = torch.zeros(max(1, npart), dtype=torch.float64, device=self.device)
+        self.keep.append(part)
+        d.partial = part.data_ptr()
+        d.out = self.l1_out.data_ptr() + 4 * op.idx
+        self._l1_fwd.append((len(self.fwd), op.idx))
+        self.fwd.append(o)
 
     # ---------------- local-window attention ----------------
     _ATTN_FWD = {"l2norm": L.ATTN_L2NORM, "corr": L.ATTN_CORR, "softmax": L.ATTN_SOFTMAX, "wnorm": L.ATTN_WNORM,
@@ -1143,7 +1187,7 @@ class Plan:
         npx = self.nf * out.H * out.W
         o.meta = dict(cls="attn", name=f"{op.kind}:{out.buf.name}", flops=0.0,
                       bytes=float(self.es * npx * (a.c + sum(b.c for b in op.bs) + out.c)))
-        return o
+        self.fwd.append(o)
 
     def _attn_backward(self, op, gout, gld):
         """Gradient contributions of one attention op (formulas in include/dvie.h)."""
@@ -1163,8 +1207,8 @@ class Plan:
 
         def contrib(region, build):
             if region.buf.needs_grad:
-                def emit(beta, res, res_ld, dact, z, z_ld):
-                    o = build(dict(res=res, res_ld=res_ld, dact=dact, z=z, z_ld=z_ld, beta=beta))
+                def emit(epi):
+                    o = build(epi._asdict())
                     o.meta = dict(cls="attn_bwd", name=f"{op.kind}:{region.buf.name}", flops=0.0,
                                   bytes=float(self.es * npx * moved))
                     return [o]
@@ -1225,7 +1269,7 @@ class Plan:
         d.running_var = m.running_var.data_ptr() if m.running_var is not None else None
         assert m.num_features == x.c or rup(m.num_features, PADC) == x.c
         assert m.num_features == x.c, "BatchNorm channel count must be a multiple of 8"
-        d.training = int(getattr(self.g, "bn_training", True))
+        d.training = int(self.g.bn_training)
         d.act, d.alpha, d.eps = op.act, 0.2, m.eps
         d.x_f32 = int(x.buf.dt == torch.float32 and self.dtype != torch.float32)
         d.momentum = m.momentum if m.momentum is not None else 0.0
@@ -1234,8 +1278,9 @@ class Plan:
     # ---------------- backward ----------------
     def _contrib(self, region, emitter, ident=None):
         """Record a gradient contribution to `region`'s buffer: either a kernel
-        (emitter(beta, res_ptr, res_ld, dact, z_ptr, z_ld) -> ops) or an identity
-        (`ident` = (ptr, ld) of a gradient region with the same shape)."""
+        (emitter(Epilogue) -> the ops to append to the backward list; called when the region's
+        last contribution is known; one that appends them itself, in order, returns []) or an
+        identity (`ident` = (ptr, ld) of a gradient region with the same shape)."""
         b = region.buf
         key = region.key()
         assert key in b.expected, (b, key)
@@ -1272,27 +1317,26 @@ class Plan:
             seq.append((em, r))
         rest = idents[k:]
         gptr, gld = self.ptr(region, grad=True), b.C
+
+        def copy_em(a):  # an identity with no kernel to ride on: a copy of its own
+            return lambda epi: [self.ew_desc(L.EW_COPY, self.nb, b.H, b.W, c, gptr, gld, [(a[0], a[1], b.H, b.W)],
+                                             **epi._asdict())]
+
         while rest:
             a = rest.pop(0)
-            r = rest.pop(0) if rest else None
-
-            def copy_em(beta, res, res_ld, dact_, z_, z_ld_, a=a):
-                return [self.ew_desc(L.EW_COPY, self.nb, b.H, b.W, c, gptr, gld, [(a[0], a[1], b.H, b.W)],
-                                     res=res, res_ld=res_ld, z=z_, z_ld=z_ld_, dact=dact_, beta=beta)]
-
-            seq.append((copy_em, r))
+            seq.append((copy_em(a), rest.pop(0) if rest else None))
         for i, (em, r) in enumerate(seq):
-            last = i == len(seq) - 1
-            ops = em(0 if i == 0 else 1, r[0] if r else None, r[1] if r else 0, dact if last else 0,
-                     z if last else None, b.C if last else 0)
-            self.bwd.extend(ops)
+            epi = Epilogue(beta=0 if i == 0 else 1, res=r[0] if r else None, res_ld=r[1] if r else 0)
+            if i == len(seq) - 1:
+                epi = epi._replace(dact=dact, z=z, z_ld=b.C)
+            self.bwd.extend(em(epi))
         b.n_flushed += 1
         b.done = b.n_flushed == len(b.expected)
 
     def _ensure_dact(self, op):
         """Producer-side activation derivative when it could not be fused upstream."""
         b = op.out.buf
-        if op.act == L.ACT_NONE or getattr(b, "dact_done", False):
+        if op.act == L.ACT_NONE or b.dact_done:
             return
         out = op.out
         gp = self.ptr(out, grad=True)
@@ -1306,9 +1350,9 @@ class Plan:
         out = {}
         if os.environ.get("DVIE_SEGENC_FUSED", "1") == "0":
             return out
-        for chain in getattr(self.g, "segenc", []):
+        for chain in self.g.segenc:
             o0, o1, o2 = chain
-            if not self._segenc_fusable(chain) or o0.x.buf.needs_grad:
+            if not segenc_fusable(self.dtype, self.nf, chain) or o0.x.buf.needs_grad:
                 continue
             if not all(op.layer.trainable for op in chain):
                 continue
@@ -1345,32 +1389,9 @@ class Plan:
                       bytes=float(self.es * npx * (8 + 32 + 32 + x.c)))
         self.bwd.append(o)
         for op, wk, bk in ((o2, "dw4", "db4"), (o1, "dw2", "db2"), (o0, "dw0", "db0")):
-            lay, xin = op.layer, op.x
-            first = lay not in self.wg_first
-            r_op = self._op(L.OP_WREDUCE)
-            r = r_op.u.wreduce
-            r.ws, r.dw, r.cmap = bufs[wk].data_ptr(), 0, lay.cmap_t.data_ptr()
-            r.splits, r.ws_rows, r.ws_k, r.co_off = slabs, lay.cout_p, 9 * xin.c, 0
-            r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, lay.cin, lay.kh, lay.kw, xin.c
-            r.beta = 0 if first else 1
-            r_op.ws_ptr = bufs[wk].data_ptr()
-            r_op.meta = _reduce_meta(lay.name, r)
-            self.bwd.append(r_op)
-            self._grad_slots.append((len(self.bwd) - 1, lay, "weight", first))
-            b_op = self._op(L.OP_WREDUCE)
-            r = b_op.u.wreduce
-            r.ws, r.dw, r.cmap = bufs[bk].data_ptr(), 0, None
-            r.splits, r.ws_rows, r.ws_k, r.co_off = slabs, lay.cout_p, 1, 0
-            r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, 1, 1, 1, 1
-            r.beta = 0 if first else 1
-            b_op.ws_ptr = bufs[bk].data_ptr()
-            b_op.meta = _reduce_meta(lay.name + ".bias", r)
-            self.bwd.append(b_op)
-            self._grad_slots.append((len(self.bwd) - 1, lay, "bias", first))
-            self.wg_first[lay] = True
-            self._uses_left[lay] -= 1
-            if self._uses_left[lay] == 0:
-                self.completions.append((len(self.bwd), lay))
+            self._reduce_op(op.layer, "weight", slabs, 9 * op.x.c, op.x.c, own=bufs[wk])
+            self._reduce_op(op.layer, "bias", slabs, own=bufs[bk])
+            self._close_layer(op.layer)
         for op in (o0, o1):  # their output gradients are never formed (d_e1 / d_e2 stay on chip)
             op.out.buf.done = True
             op.out.buf.dact_done = True
@@ -1378,12 +1399,8 @@ class Plan:
 
     def _build_backward(self):
         g = self.g
-        nb = self.nb
         seg_bwd = self._seg_bwd
         seg_skip = {id(op) for ch in seg_bwd.values() for op in ch[:2]}
-        self.wg_first = {}
-        self.completions = []  # (bwd index, layer): the layer's parameter gradients are final
-        self._uses_left = {}
         for op in g.ops:
             if isinstance(op, (ConvOp, ConvTOp)) and op.layer.trainable:
                 self._uses_left[op.layer] = self._uses_left.get(op.layer, 0) + 1
@@ -1391,141 +1408,151 @@ class Plan:
             b = region.buf
             assert b.needs_grad and not b.expected
             assert b.t is not None or all(p.act == L.ACT_NONE for p in b.producers), "external output with activation"
-            o = self.ew_desc(L.EW_NCHW, nb, region.H, region.W, region.c, self.ptr(region, grad=True), b.C)
+            o = self.ew_desc(L.EW_NCHW, self.nb, region.H, region.W, region.c, self.ptr(region, grad=True), b.C)
             o.u.ew.ext_c = ch
             self.ext_ograd[key] = len(self.bwd)
             self.bwd.append(o)
             b.done = True
             b.dact_done = all(p.act == L.ACT_NONE for p in b.producers)  # else _ensure_dact at the producer
         for op in reversed(g.ops):
-            if isinstance(op, OutNCHWOp):
-                continue
-            if isinstance(op, HeadOp):
-                x = op.x
-                if not x.buf.needs_grad:
-                    continue
-                xg = self.ptr(x, grad=True)
-
-                def em(beta, res, res_ld, dact, z, z_ld, op=op, x=x, xg=xg):
-                    assert res is None and dact == 0, "head backward has no fused epilogue"
-                    o = self._op(L.OP_HEAD_BWD)
-                    d = o.u.head
-                    d.gx, d.gx_ld = xg, x.buf.C
-                    d.n, d.h, d.w, d.c, d.pool, d.dtype, d.beta = nb, x.H, x.W, x.c, op.pool, self.dt, beta
-                    self.ext_head_grad = getattr(self, "ext_head_grad", {})
-                    self.ext_head_grad[op.key] = len(self.bwd)
-                    return [o]
-
-                self._contrib(x, em)
-                continue
-            if isinstance(op, L1FeatOp):
-                a = op.a
-                if not a.buf.needs_grad:
-                    continue
-                numel = (self.nf // 2) * a.H * a.W * a.c
-                ap, bp, ld = self.ptr(a, 0), self.ptr(a, self.nf // 2), a.buf.C
-                gp = self.ptr(a, grad=True)
-                scale = op.weight / numel
-
-                def em(beta, res, res_ld, dact, z, z_ld, a=a, ap=ap, bp=bp, ld=ld, gp=gp, scale=scale):
-                    o = self.ew_desc(L.EW_L1SIGN, nb, a.H, a.W, a.c, gp, ld, [(ap, ld, a.H, a.W), (bp, ld, a.H, a.W)],
-                                     res=res, res_ld=res_ld, z=z, z_ld=z_ld, dact=dact, beta=beta, scale=scale)
-                    o.l1_seed = scale  # set_l1_loss rescales the seeds of the backward
-                    return [o]
-
-                self._contrib(a, em)
-                continue
+            lower = self._BWD.get(type(op))
+            if lower is None:
+                raise TypeError(op)
             out = op.out
+            if out is None:  # a sink: it has no gradient of its own to wait for
+                lower(self, op, None, 0)
+                continue
             b = out.buf
-            if not b.needs_grad or not getattr(b, "done", False):
+            if not b.needs_grad or not b.done:
                 continue  # no gradient reaches this op
             if id(op) in seg_skip:
                 continue  # inside a fused encoder backward: its gradient is never formed
             self._ensure_dact(op)
             gout, gld = self.ptr(out, grad=True), b.C
-            if isinstance(op, InputOp):
-                if op.requires_grad:
-                    o = self.ew_desc(L.EW_TONCHW, nb, out.H, out.W, out.c, 0, 0, [(gout, gld, out.H, out.W)])
-                    o.u.ew.ext_c = op.ext_c
-                    if op.normalize:
-                        o.u.ew.std = op.std_t.data_ptr()
-                    self.ext_grad.setdefault(op.key, []).append((len(self.bwd), op))
-                    self.bwd.append(o)
-                continue
             if id(op) in seg_bwd:
                 self._segenc_backward(seg_bwd[id(op)], gout, gld)
-                continue
-            if isinstance(op, ConvOp):
-                self._conv_backward(op, gout, gld)
-            elif isinstance(op, ConvTOp):
-                self._convT_backward(op, gout, gld)
-            elif isinstance(op, BNOp):
-                x = op.x
-                assert len(x.buf.consumers) == 1, "BatchNorm input must have no other reader"
-                xg = self.ptr(x, grad=True) if x.buf.needs_grad else None
-                if x.buf.needs_grad:
-                    def em(beta, res, res_ld, dact, z, z_ld, op=op, x=x, xg=xg, gout=gout, gld=gld):
-                        assert res is None and dact == 0, "BatchNorm backward has no fused epilogue"
-                        o = self._op(L.OP_BN_BWD)
-                        d = o.u.bn
-                        self._bn_common(d, op, nb)
-                        d.g, d.g_ld = gout, gld
-                        d.dx, d.dx_ld, d.beta_dx = xg, x.buf.C, beta
-                        if op.trainable:
-                            self._grad_slots.append((len(self.bwd), op.m, "bn", op.m not in self.wg_first))
-                            self.wg_first[op.m] = True
-                        return [o]
-
-                    self._contrib(x, em)
-            elif isinstance(op, AttnOp):
-                self._attn_backward(op, gout, gld)
-            elif isinstance(op, FuseOp):
-                if op.detach:
-                    continue
-                for s in op.srcs:
-                    if not s.buf.needs_grad:
-                        continue
-                    if (s.H, s.W) == (out.H, out.W):
-                        self._contrib(s, None, ident=(gout, gld))
-                    else:
-                        sp = self.ptr(s, grad=True)
-
-                        def em(beta, res, res_ld, dact, z, z_ld, s=s, sp=sp, out=out, gout=gout, gld=gld, op=op):
-                            o = self.ew_desc(L.EW_UPT, nb, s.H, s.W, s.c, sp, s.buf.C, [(gout, gld, out.H, out.W)],
-                                             res=res, res_ld=res_ld, z=z, z_ld=z_ld, dact=dact, beta=beta)
-                            o.u.ew.align = int(op.align)
-                            return [o]
-
-                        self._contrib(s, em)
-            elif isinstance(op, MaskOp):
-                src = op.src
-                if src.buf.needs_grad:
-                    sp = self.ptr(src, grad=True)
-
-                    def em(beta, res, res_ld, dact, z, z_ld, src=src, sp=sp, out=out, gout=gout, gld=gld, op=op):
-                        o = self.ew_desc(L.EW_MASK, nb, src.H, src.W, src.c, sp, src.buf.C, [(gout, gld, out.H, out.W)],
-                                         res=res, res_ld=res_ld, z=z, z_ld=z_ld, dact=dact, beta=beta)
-                        o.u.ew.ext_c = int(op.inverse)
-                        self.ext_mask = getattr(self, "ext_mask", {})
-                        self.ext_mask.setdefault(op.key, []).append(("bwd", len(self.bwd), op))
-                        return [o]
-
-                    self._contrib(src, em)
-            elif isinstance(op, PoolOp):
-                x = op.x
-                if x.buf.needs_grad:
-                    xp = self.ptr(x, grad=True)
-
-                    def em(beta, res, res_ld, dact, z, z_ld, x=x, xp=xp, out=out, gout=gout, gld=gld):
-                        return [self.ew_desc(L.EW_POOLT, nb, x.H, x.W, x.c, xp, x.buf.C, [(gout, gld, out.H, out.W)],
-                                             res=res, res_ld=res_ld, z=z, z_ld=z_ld, dact=dact, beta=beta)]
-
-                    self._contrib(x, em)
+            else:
+                lower(self, op, gout, gld)
         # (buffers whose contributions never completed would indicate a graph bug)
         for bf in g.buffers:
-            if bf.needs_grad and bf.expected and not getattr(bf, "done", False):
+            if bf.needs_grad and bf.expected and not bf.done:
                 raise RuntimeError(f"incomplete gradient for {bf}: pending {({k: len(v) for k, v in bf.pending.items()})}"
                                    f" of {bf.expected}")
+
+    def _out_nchw_backward(self, op, gout, gld):
+        pass  # (an output's gradient is seeded in _build_backward; an export has none)
+
+    def _head_backward(self, op, gout, gld):
+        x = op.x
+        if not x.buf.needs_grad:
+            return
+        xg = self.ptr(x, grad=True)
+
+        def em(epi):
+            assert epi.res is None and epi.dact == 0, "head backward has no fused epilogue"
+            o = self._op(L.OP_HEAD_BWD)
+            d = o.u.head
+            d.gx, d.gx_ld = xg, x.buf.C
+            d.n, d.h, d.w, d.c, d.pool, d.dtype, d.beta = self.nb, x.H, x.W, x.c, op.pool, self.dt, epi.beta
+            self.ext_head_grad[op.key] = len(self.bwd)
+            return [o]
+
+        self._contrib(x, em)
+
+    def _l1feat_backward(self, op, gout, gld):
+        a = op.a
+        if not a.buf.needs_grad:
+            return
+        numel = (self.nf // 2) * a.H * a.W * a.c
+        ap, bp, ld = self.ptr(a, 0), self.ptr(a, self.nf // 2), a.buf.C
+        gp = self.ptr(a, grad=True)
+        scale = op.weight / numel
+
+        def em(epi):
+            o = self.ew_desc(L.EW_L1SIGN, self.nb, a.H, a.W, a.c, gp, ld, [(ap, ld, a.H, a.W), (bp, ld, a.H, a.W)],
+                             scale=scale, **epi._asdict())
+            o.l1_seed = scale  # set_l1_loss rescales the seeds of the backward
+            return [o]
+
+        self._contrib(a, em)
+
+    def _input_backward(self, op, gout, gld):
+        if not op.requires_grad:
+            return
+        out = op.out
+        o = self.ew_desc(L.EW_TONCHW, self.nb, out.H, out.W, out.c, 0, 0, [(gout, gld, out.H, out.W)])
+        o.u.ew.ext_c = op.ext_c
+        if op.normalize:
+            o.u.ew.std = op.std_t.data_ptr()
+        self.ext_grad.setdefault(op.key, []).append((len(self.bwd), op))
+        self.bwd.append(o)
+
+    def _bn_backward(self, op, gout, gld):
+        x = op.x
+        assert len(x.buf.consumers) == 1, "BatchNorm input must have no other reader"
+        if not x.buf.needs_grad:
+            return
+        xg = self.ptr(x, grad=True)
+
+        def em(epi):
+            assert epi.res is None and epi.dact == 0, "BatchNorm backward has no fused epilogue"
+            o = self._op(L.OP_BN_BWD)
+            d = o.u.bn
+            self._bn_common(d, op, self.nb)
+            d.g, d.g_ld = gout, gld
+            d.dx, d.dx_ld, d.beta_dx = xg, x.buf.C, epi.beta
+            if op.trainable:
+                self._grad_slots.append((len(self.bwd), op.m, "bn", op.m not in self.wg_first))
+                self.wg_first[op.m] = True
+            return [o]
+
+        self._contrib(x, em)
+
+    def _fuse_backward(self, op, gout, gld):
+        if op.detach:
+            return
+        out = op.out
+
+        def resize_t(s):  # the adjoint of the bilinear resize of s to out's grid
+            sp = self.ptr(s, grad=True)
+
+            def em(epi):
+                o = self.ew_desc(L.EW_UPT, self.nb, s.H, s.W, s.c, sp, s.buf.C, [(gout, gld, out.H, out.W)],
+                                 **epi._asdict())
+                o.u.ew.align = int(op.align)
+                return [o]
+            return em
+
+        for s in op.srcs:
+            if not s.buf.needs_grad:
+                continue
+            if (s.H, s.W) == (out.H, out.W):
+                self._contrib(s, None, ident=(gout, gld))
+            else:
+                self._contrib(s, resize_t(s))
+
+    def _mask_backward(self, op, gout, gld):
+        src, out = op.src, op.out
+        if not src.buf.needs_grad:
+            return
+        sp = self.ptr(src, grad=True)
+
+        def em(epi):
+            o = self.ew_desc(L.EW_MASK, self.nb, src.H, src.W, src.c, sp, src.buf.C, [(gout, gld, out.H, out.W)],
+                             **epi._asdict())
+            o.u.ew.ext_c = int(op.inverse)
+            self.ext_mask.setdefault(op.key, []).append(("bwd", len(self.bwd), op))
+            return [o]
+
+        self._contrib(src, em)
+
+    def _pool_backward(self, op, gout, gld):
+        x, out = op.x, op.out
+        if not x.buf.needs_grad:
+            return
+        xp = self.ptr(x, grad=True)
+        self._contrib(x, lambda epi: [self.ew_desc(L.EW_POOLT, self.nb, x.H, x.W, x.c, xp, x.buf.C,
+                                                   [(gout, gld, out.H, out.W)], **epi._asdict())])
 
     def _head3_fusable(self, op, gld):
         """Narrow-output 3x3 head conv (HRNet rgb_layer[2] / seg_layer[2]) whose backward can
@@ -1547,119 +1574,85 @@ class Plan:
         npx = self.nb * x.H * x.W
         return npx * max(x.buf.C, gld) * 2 < 0xFFFFFF00
 
-    def _head3_ops(self, op, gout, gld, phase, xg, dact):
+    def _emit_head3(self, op, gout, gld, phase, xg, dact):
         """dvie_head3_bwd (data gradient with act' + weight-gradient slabs in one pass over
         the input) into its own slab buffer, then on the weight lane the bias column sums and
-        the slab reductions; the weight-gradient bookkeeping of _emit_wgrad."""
-        lay, x, out = op.layer, op.x, op.out
-        nb = self.nb
+        the slab reductions."""
+        lay, x = op.layer, op.x
         ph, wt, kpad = phase
-        n_cb = x.c // 64
-        splits = max(1, 256 // n_cb)
+        splits = max(1, 256 // (x.c // 64))
         slabs = torch.empty(splits * lay.cout_p * 9 * x.c, dtype=torch.float32, device=self.device)
         self.keep.append(slabs)
         o = self._op(L.OP_HEAD3_BWD)
         d = o.u.head3
         d.g, d.h, d.wd, d.dh, d.ws = gout, self.ptr(x), wt.data_ptr(), xg, slabs.data_ptr()
         d.g_ld, d.h_ld, d.dh_ld = gld, x.buf.C, x.buf.C
-        d.n, d.hgt, d.wid, d.c = nb, x.H, x.W, x.c
+        d.n, d.hgt, d.wid, d.c = self.nb, x.H, x.W, x.c
         d.cout, d.kpad, d.dy0, d.dx0 = lay.cout_p, kpad, ph["dy0"], ph["dx0"]
         d.splits, d.dact, d.alpha = splits, dact, 0.2
-        npix = nb * x.H * x.W
+        npix = self.nb * x.H * x.W
         o.meta = dict(cls="conv_dgrad", name=lay.name + "+wgrad",
                       flops=2.0 * npix * lay.cout * lay.cin * 9 * 2,
                       bytes=float(self.es * (2 * npix * x.c + npix * lay.cout) + 4 * slabs.numel()))
-        ops = [o]
-        first = lay not in self.wg_first
-        base = len(self.bwd)
+        self.bwd.append(o)
+        csplits = self._colsum_op(gout, gld, npix, lay.cout_p) if lay.has_bias else 0
+        self._reduce_op(lay, "weight", splits, 9 * x.c, x.c, own=slabs)
         if lay.has_bias:
-            csplits = max(1, min(2048, npix // 512))
-            c = self._op(L.OP_COLSUM)
-            cd = c.u.colsum
-            cd.g, cd.ws, cd.g_ld, cd.rows, cd.c, cd.splits, cd.dtype = gout, 0, gld, npix, lay.cout_p, csplits, self.dt
-            self.ws_floats = max(self.ws_floats, csplits * lay.cout_p)
-            ops.append(c)
-        r_op = self._op(L.OP_WREDUCE)
-        r = r_op.u.wreduce
-        r.ws, r.dw, r.cmap = slabs.data_ptr(), 0, lay.cmap_t.data_ptr()
-        r.splits, r.ws_rows, r.ws_k, r.co_off = splits, lay.cout_p, 9 * x.c, 0
-        r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, lay.cin, lay.kh, lay.kw, x.c
-        r.beta = 0 if first else 1
-        r_op.ws_ptr = slabs.data_ptr()
-        r_op.meta = _reduce_meta(lay.name, r)
-        ops.append(r_op)
-        self._grad_slots.append((base + len(ops) - 1, lay, "weight", first))
-        if lay.has_bias:
-            b_op = self._op(L.OP_WREDUCE)
-            r = b_op.u.wreduce
-            r.ws, r.dw, r.cmap = 0, 0, None
-            r.splits, r.ws_rows, r.ws_k, r.co_off = csplits, lay.cout_p, 1, 0
-            r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, 1, 1, 1, 1
-            r.beta = 0 if first else 1
-            b_op.meta = _reduce_meta(lay.name + ".bias", r)
-            ops.append(b_op)
-            self._grad_slots.append((base + len(ops) - 1, lay, "bias", first))
-        self.wg_first[lay] = True
-        self._uses_left[lay] -= 1
-        if self._uses_left[lay] == 0:
-            self.completions.append((base + len(ops), lay))
-        return ops
+            self._reduce_op(lay, "bias", csplits)
+        self._close_layer(lay)
 
     def _conv_backward(self, op, gout, gld):
         lay, x, out = op.layer, op.x, op.out
         nb = self.nb
-        npix = nb * out.H * out.W
-        taps = lay.fwd_taps()
         head3 = self._head3_fusable(op, gld)
         if lay.trainable and not head3:
             self._emit_wgrad(op, gout, gld)
         if op.res is not None and op.res.buf.needs_grad:
             self._contrib(op.res, None, ident=(gout, gld))
-        if x.buf.needs_grad:
-            phases = self._dgrad_weights(lay, x.H, x.W)
-            xg = self.ptr(x, grad=True)
+        if not x.buf.needs_grad:
+            return
+        phases = self._dgrad_weights(lay, x.H, x.W)
+        xg = self.ptr(x, grad=True)
 
-            def em(beta, res, res_ld, dact, z, z_ld, phases=phases, x=x, xg=xg, out=out, gout=gout, gld=gld, lay=lay):
-                if head3:
-                    if beta == 0 and res is None and dact in (L.ACT_NONE, L.ACT_LRELU) and \
-                            (z is None or z == self.ptr(x)) and len(phases) == 1:
-                        return self._head3_ops(op, gout, gld, phases[0], xg, dact)
-                    self._emit_wgrad(op, gout, gld)  # (not the expected pattern: unfused)
-                ops = []
-                if self._im2col_dgrad(lay, x, phases):
-                    return self._im2col_dgrad_ops(lay, x, xg, out, gout, gld, phases[0], res, res_ld, z, z_ld, dact,
-                                                  beta)
-                if self._ph4_eligible(lay, x):
-                    wt, kpad = self._dgrad_weights_ph4(lay)
-                    taps = dict(th=2, tw=2, dy0=0, dx0=0, ddy=1, ddx=1)
-                    o = self.conv_desc(gout, gld, nb, out.H, out.W, lay.cout_p, wt.data_ptr(), kpad, 4 * x.c, out.H,
-                                       out.W, 1, 1, taps, xg, x.buf.C, x.H, x.W, osy=2, osx=2, res=res, res_ld=res_ld,
-                                       z=z, z_ld=z_ld, dact=dact, beta=beta)
-                    o.u.conv.phc = x.c
-                    npx = nb * x.H * x.W
-                    o.meta = dict(cls="conv_dgrad", name=lay.name,
-                                  flops=2.0 * nb * out.H * out.W * lay.cin * lay.cout * 9,
-                                  bytes=float(self.es * (nb * out.H * out.W * lay.cout
-                                                         + npx * lay.cin * (1 + (res is not None) + (z is not None) + beta)
-                                                         + lay.cout * lay.cin * 9)))
-                    return [o]
-                for ph, wt, kpad in phases:
-                    o = self.conv_desc(
-                        gout, gld, nb, out.H, out.W, lay.cout_p, wt.data_ptr(), kpad, x.c, ph["oh"], ph["ow"], 1, 1,
-                        ph, xg, x.buf.C, x.H, x.W, osy=lay.stride, osx=lay.stride, ory=ph["ry"], orx=ph["rx"],
-                        res=res, res_ld=res_ld, z=z, z_ld=z_ld, dact=dact, beta=beta)
-                    npx = nb * ph["oh"] * ph["ow"]
-                    frac = npx / float(nb * x.H * x.W)
-                    o.meta = dict(cls="conv_dgrad",
-                                  name=lay.name + (f" [phase {ph['ry']}{ph['rx']}]" if len(phases) > 1 else ""),
-                                  flops=2.0 * npx * lay.cin * lay.cout * ph["th"] * ph["tw"],
-                                  bytes=float(self.es * (frac * nb * out.H * out.W * lay.cout
-                                                         + npx * lay.cin * (1 + (res is not None) + (z is not None) + beta)
-                                                         + lay.cout * lay.cin * ph["th"] * ph["tw"])))
-                    ops.append(o)
-                return ops
+        def em(epi):
+            if head3:
+                if epi.beta == 0 and epi.res is None and epi.dact in (L.ACT_NONE, L.ACT_LRELU) and \
+                        (epi.z is None or epi.z == self.ptr(x)) and len(phases) == 1:
+                    self._emit_head3(op, gout, gld, phases[0], xg, epi.dact)
+                    return []  # (appended in place: the reductions' slots are backward indices)
+                self._emit_wgrad(op, gout, gld)  # (not the expected pattern: unfused)
+            extra = (epi.res is not None) + (epi.z is not None) + epi.beta  # further passes over the gradient
+            if self._im2col_dgrad(lay, x, phases):
+                return self._im2col_dgrad_ops(lay, x, xg, out, gout, gld, phases[0], epi)
+            if self._ph4_eligible(lay, x):
+                wt, kpad = self._dgrad_weights_ph4(lay)
+                taps = dict(th=2, tw=2, dy0=0, dx0=0, ddy=1, ddx=1)
+                o = self.conv_desc(gout, gld, nb, out.H, out.W, lay.cout_p, wt.data_ptr(), kpad, 4 * x.c, out.H,
+                                   out.W, 1, 1, taps, xg, x.buf.C, x.H, x.W, osy=2, osx=2, **epi._asdict())
+                o.u.conv.phc = x.c
+                npx = nb * x.H * x.W
+                o.meta = dict(cls="conv_dgrad", name=lay.name,
+                              flops=2.0 * nb * out.H * out.W * lay.cin * lay.cout * 9,
+                              bytes=float(self.es * (nb * out.H * out.W * lay.cout + npx * lay.cin * (1 + extra)
+                                                     + lay.cout * lay.cin * 9)))
+                return [o]
+            ops = []
+            for ph, wt, kpad in phases:
+                o = self.conv_desc(
+                    gout, gld, nb, out.H, out.W, lay.cout_p, wt.data_ptr(), kpad, x.c, ph["oh"], ph["ow"], 1, 1,
+                    ph, xg, x.buf.C, x.H, x.W, osy=lay.stride, osx=lay.stride, ory=ph["ry"], orx=ph["rx"],
+                    **epi._asdict())
+                npx = nb * ph["oh"] * ph["ow"]
+                frac = npx / float(nb * x.H * x.W)
+                o.meta = dict(cls="conv_dgrad",
+                              name=lay.name + (f" [phase {ph['ry']}{ph['rx']}]" if len(phases) > 1 else ""),
+                              flops=2.0 * npx * lay.cin * lay.cout * ph["th"] * ph["tw"],
+                              bytes=float(self.es * (frac * nb * out.H * out.W * lay.cout + npx * lay.cin * (1 + extra)
+                                                     + lay.cout * lay.cin * ph["th"] * ph["tw"])))
+                ops.append(o)
+            return ops
 
-            self._contrib(x, em)
+        self._contrib(x, em)
 
     def _wgrad_s2_eligible(self, lay, x, out):
         """stride-2 3x3 pad-1 weight gradient as its four input phases on the halo kernel
@@ -1676,6 +1669,85 @@ class Plan:
                 and x.H % 2 == 0 and x.W % 2 == 0 and out.H == x.H // 2 and out.W == x.W // 2 and out.W % 64 == 0
                 and x.c % 8 == 0 and x.buf.C % 8 == 0)
 
+    # ---- weight-gradient emission: a slab writer (_wgrad_op / _colsum_op / a fused kernel with
+    # its own buffer), one _reduce_op per parameter, _close_layer.  _batch_reductions derives
+    # the slab regions from the order of the writers and reductions in the list. ----
+    def _wgrad_op(self, g, g_ld, x, x_ld, oh, ow, cout, ih, iw, c, stride, taps, bias=False, ws_taps=0, tmap=0,
+                  need_hint=False):
+        """One WGRAD op over self.nb images -> (op, slabs, bias slabs): the output-gradient
+        operand g (oh x ow x cout) against the input operand x (ih x iw x c) under `taps`,
+        split as the library hints (need_hint: the halo kernel, which gives the hint, must take
+        the launch), else by the split-K formula.  ws_taps / tmap: the launch fills its taps'
+        column blocks of a slab set of ws_taps taps (include/dvie.h).  bias: it also writes
+        g's column sums, after the weight slabs."""
+        o = self._op(L.OP_WGRAD)
+        d = o.u.wgrad
+        d.g, d.x, d.ws = g, x, 0
+        d.g_ld, d.x_ld = g_ld, x_ld
+        d.n, d.oh, d.ow, d.cout = self.nb, oh, ow, cout
+        d.ih, d.iw, d.c, d.sy, d.sx = ih, iw, c, stride, stride
+        d.th, d.tw, d.dy0, d.dx0, d.ddy, d.ddx = (taps[k] for k in ("th", "tw", "dy0", "dx0", "ddy", "ddx"))
+        d.tmap, d.ws_taps, d.dtype = tmap, ws_taps, self.dt
+        lib = L.load()
+        hint = lib.dvie_wgrad_splits_hint(ctypes.byref(d))
+        assert hint > 0 or not need_hint, "the halo weight-gradient kernel refused a launch lowered for it"
+        ntap = taps["th"] * taps["tw"]
+        tiles = rup(cout, 64) // 64 * (rup(c, 64) // 64)
+        bkp = 64 if self.dtype == torch.bfloat16 else 32
+        d.splits = hint if hint > 0 else max(1, min(max(1, self.nb * oh * ow // (bkp * 4)),
+                                                    1024 // max(1, tiles * ntap)))
+        slabs = lib.dvie_wgrad_slabs(ctypes.byref(d))
+        wfl = slabs * cout * (ws_taps or ntap) * c
+        bslabs = 0
+        if bias:
+            d.bws = 1  # placeholder (set in _finalize): makes the query see a bias launch
+            bslabs = lib.dvie_wgrad_bias_slabs(ctypes.byref(d))
+            d.bws = None
+            o.bws_off = wfl
+        self.ws_floats = max(self.ws_floats, wfl + bslabs * cout)
+        return o, slabs, bslabs
+
+    def _colsum_op(self, g, g_ld, rows, c):
+        """append the column sums of g ([rows][c]) as partial slabs in the workspace -> their count"""
+        splits = max(1, min(2048, rows // 512))
+        o = self._op(L.OP_COLSUM)
+        d = o.u.colsum
+        d.g, d.ws, d.g_ld, d.rows, d.c, d.splits, d.dtype = g, 0, g_ld, rows, c, splits, self.dt
+        self.ws_floats = max(self.ws_floats, splits * c)
+        self.bwd.append(o)
+        return splits
+
+    def _reduce_op(self, lay, which, splits, ws_k=1, c=1, ws_off=0, own=None):
+        """Append the reduction of `splits` partial slabs into the layer's 'weight' or 'bias'
+        .grad view and record its gradient slot.  Weight slabs are [cout_p][ws_k] over c packed
+        input channels, bias slabs one column.  They lie in the shared workspace, ws_off floats
+        into the region of the writer before this op, or in the site's `own` tensor."""
+        o = self._op(L.OP_WREDUCE)
+        r = o.u.wreduce
+        if which == "weight":
+            rows, r.cmap = lay.cout_p, lay.cmap_t.data_ptr()
+            r.cout_p, r.cin_p, r.kh_n, r.kw_n = lay.cout, lay.cin, lay.kh, lay.kw
+        else:  # (a transposed conv's bias belongs to its output = the virtual conv's input)
+            rows, r.cout_p = (lay.cin_p, lay.cin) if lay.transposed else (lay.cout_p, lay.cout)
+            r.cmap, r.cin_p, r.kh_n, r.kw_n = None, 1, 1, 1
+        r.splits, r.ws_rows, r.ws_k, r.co_off, r.c = splits, rows, ws_k, 0, c
+        first = lay not in self.wg_first
+        r.beta = 0 if first else 1
+        o.ws_off = ws_off
+        if own is not None:
+            o.ws_ptr = r.ws = own.data_ptr()
+        o.meta = _reduce_meta(lay.name + (".bias" if which == "bias" else ""), r)
+        self.bwd.append(o)
+        self._grad_slots.append((len(self.bwd) - 1, lay, which, first))
+
+    def _close_layer(self, lay):
+        """one use of the layer has its reductions in the list; after the last use the
+        layer's parameter gradients are final"""
+        self.wg_first[lay] = True
+        self._uses_left[lay] -= 1
+        if self._uses_left[lay] == 0:
+            self.completions.append((len(self.bwd), lay))
+
     def _emit_wgrad_s2(self, op, gout, gld):
         """The stride-2 weight gradient as four stride-1 launches, one per input phase
         (a, b): tap (i, j) of phase (a, b) is forward tap (kh, kw) = (1, .) for a = 0, (0 | 2, .)
@@ -1683,139 +1755,50 @@ class Plan:
         (x + (a W + b) ld, x_ld 2 ld, iw = W as the row pitch); each launch fills its taps'
         column blocks of one [splits][cout][9 c] slab set, reduced once."""
         lay, x, out = op.layer, op.x, op.out
-        nb = self.nb
-        npix = nb * out.H * out.W
-        lib = L.load()
-        ops, slabs, bslabs = [], None, 0
+        npix = self.nb * out.H * out.W
+        slabs, bslabs = None, 0
         for a in (0, 1):
             for b in (0, 1):
-                o = self._op(L.OP_WGRAD)
-                d = o.u.wgrad
-                d.g, d.x, d.ws = gout, self.ptr(x) + (a * x.W + b) * x.buf.C * self.es, 0
-                d.g_ld, d.x_ld = gld, 2 * x.buf.C
-                d.n, d.oh, d.ow, d.cout = nb, out.H, out.W, lay.cout_p
-                d.ih, d.iw, d.c, d.sy, d.sx = x.H // 2, x.W, x.c, 1, 1
-                d.th, d.tw, d.dy0, d.dx0, d.ddy, d.ddx = 1 + a, 1 + b, -a, -b, 1, 1
                 khs, kws = ([1] if a == 0 else [0, 2]), ([1] if b == 0 else [0, 2])
-                d.tmap = sum((kh * 3 + kw) << (4 * (i * len(kws) + j)) for i, kh in enumerate(khs)
-                             for j, kw in enumerate(kws))
-                d.ws_taps = 9
-                d.dtype = self.dt
-                hint = lib.dvie_wgrad_splits_hint(ctypes.byref(d))
-                assert hint > 0, f"{lay.name}: the halo weight-gradient kernel refused a stride-2 phase launch"
-                d.splits = hint
-                n_s = lib.dvie_wgrad_slabs(ctypes.byref(d))
+                tmap = sum((kh * 3 + kw) << (4 * (i * len(kws) + j)) for i, kh in enumerate(khs)
+                           for j, kw in enumerate(kws))
+                # (the bias column sums ride on one launch)
+                o, n_s, n_b = self._wgrad_op(
+                    gout, gld, self.ptr(x) + (a * x.W + b) * x.buf.C * self.es, 2 * x.buf.C, out.H, out.W, lay.cout_p,
+                    x.H // 2, x.W, x.c, 1, dict(th=1 + a, tw=1 + b, dy0=-a, dx0=-b, ddy=1, ddx=1),
+                    bias=lay.has_bias and (a, b) == (0, 0), ws_taps=9, tmap=tmap, need_hint=True)
                 assert slabs in (None, n_s), "stride-2 phase launches disagree on their slab count"
-                slabs = n_s
-                if a == 0 and b == 0 and lay.has_bias:  # the bias column sums ride on one launch
-                    d.bws = 1
-                    bslabs = lib.dvie_wgrad_bias_slabs(ctypes.byref(d))
-                    d.bws = None
-                    o.bws_off = slabs * lay.cout_p * 9 * x.c
+                slabs, bslabs = n_s, max(bslabs, n_b)
                 nt = len(khs) * len(kws)
                 o.meta = dict(cls="conv_wgrad", name=lay.name + f" [phase {a}{b}]",
                               flops=2.0 * npix * lay.cout * lay.cin * nt,
                               bytes=float(self.es * (npix * lay.cout + npix * lay.cin)
                                           + 4 * slabs * lay.cout_p * nt * x.c))
-                ops.append(o)
-        wfl = slabs * lay.cout_p * 9 * x.c
-        self.ws_floats = max(self.ws_floats, wfl + bslabs * lay.cout_p)
-        self.bwd += ops
-        self._emit_wreduce(lay, slabs, 9 * x.c, x.c, bslabs, wfl)
-
-    def _emit_wreduce(self, lay, slabs, ws_k, c, bslabs, bias_off):
-        """the slab reductions of a weight gradient (and of its bias partials) into the .grad
-        views, and the layer's completion bookkeeping"""
-        o = self._op(L.OP_WREDUCE)
-        r = o.u.wreduce
-        r.ws, r.dw, r.cmap = 0, 0, lay.cmap_t.data_ptr()
-        r.splits, r.ws_rows, r.ws_k, r.co_off = slabs, lay.cout_p, ws_k, 0
-        r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, lay.cin, lay.kh, lay.kw, c
-        first = lay not in self.wg_first
-        r.beta = 0 if first else 1
-        o.meta = _reduce_meta(lay.name, r)
-        self.bwd.append(o)
-        self._grad_slots.append((len(self.bwd) - 1, lay, "weight", first))
+                self.bwd.append(o)
+        self._reduce_op(lay, "weight", slabs, 9 * x.c, x.c)
         if lay.has_bias:
-            o = self._op(L.OP_WREDUCE)
-            r = o.u.wreduce
-            r.ws, r.dw, r.cmap = 0, 0, None
-            r.splits, r.ws_rows, r.ws_k, r.co_off = bslabs, lay.cout_p, 1, 0
-            r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, 1, 1, 1, 1
-            r.beta = 0 if first else 1
-            o.meta = _reduce_meta(lay.name + ".bias", r)
-            o.ws_off = bias_off
-            self.bwd.append(o)
-            self._grad_slots.append((len(self.bwd) - 1, lay, "bias", first))
-        self.wg_first[lay] = True
-        self._uses_left[lay] -= 1
-        if self._uses_left[lay] == 0:
-            self.completions.append((len(self.bwd), lay))
+            self._reduce_op(lay, "bias", bslabs, ws_off=slabs * lay.cout_p * 9 * x.c)
+        self._close_layer(lay)
 
     def _emit_wgrad(self, op, gout, gld):
-        """weight (and bias) gradient of a conv: split-K partial slabs + reduction into the
-        OIHW .grad view, appended to the backward list (weight lane)."""
+        """weight (and bias) gradient of a conv: split-K partial slabs (the bias column sums
+        ride on the weight-gradient launch) + reduction into the OIHW .grad view, appended to
+        the backward list (weight lane)."""
         lay, x, out = op.layer, op.x, op.out
         if self._wgrad_s2_eligible(lay, x, out) and gld % 8 == 0:
             return self._emit_wgrad_s2(op, gout, gld)
-        nb = self.nb
-        npix = nb * out.H * out.W
-        taps = lay.fwd_taps()
-        # weight gradient: split-K partial slabs + reduction into the OIHW .grad view
-        tiles = rup(lay.cout_p, 64) // 64 * (rup(x.c, 64) // 64)
+        o, slabs, bslabs = self._wgrad_op(gout, gld, self.ptr(x), x.buf.C, out.H, out.W, lay.cout_p, x.H, x.W, x.c,
+                                          lay.stride, lay.fwd_taps(), bias=lay.has_bias)
+        npix = self.nb * out.H * out.W
         ntap = lay.kh * lay.kw
-        bkp = 64 if self.dtype == torch.bfloat16 else 32
-        splits = max(1, min(max(1, npix // (bkp * 4)), 1024 // max(1, tiles * ntap)))
-        o = self._op(L.OP_WGRAD)
-        d = o.u.wgrad
-        d.g, d.x, d.ws = gout, self.ptr(x), 0
-        d.g_ld, d.x_ld = gld, x.buf.C
-        d.n, d.oh, d.ow, d.cout = nb, out.H, out.W, lay.cout_p
-        d.ih, d.iw, d.c, d.sy, d.sx = x.H, x.W, x.c, lay.stride, lay.stride
-        d.th, d.tw, d.dy0, d.dx0, d.ddy, d.ddx = taps["th"], taps["tw"], taps["dy0"], taps["dx0"], taps["ddy"], \
-            taps["ddx"]
-        d.dtype = self.dt
-        lib = L.load()
-        hint = lib.dvie_wgrad_splits_hint(ctypes.byref(d))  # the halo kernel's preferred split
-        d.splits = hint if hint > 0 else splits
-        slabs = lib.dvie_wgrad_slabs(ctypes.byref(d))
-        wfl = slabs * lay.cout_p * ntap * x.c
-        bslabs = 0
-        if lay.has_bias:  # bias column sums ride on the weight-gradient launch (d.bws)
-            d.bws = 1  # placeholder (set in _finalize): makes the query see a bias launch
-            bslabs = lib.dvie_wgrad_bias_slabs(ctypes.byref(d))
-            d.bws = None
-            o.bws_off = wfl
-        self.ws_floats = max(self.ws_floats, wfl + bslabs * lay.cout_p)
         o.meta = dict(cls="conv_wgrad", name=lay.name, flops=2.0 * npix * lay.cout * lay.cin * ntap,
-                      bytes=float(self.es * (npix * lay.cout + nb * x.H * x.W * lay.cin)
+                      bytes=float(self.es * (npix * lay.cout + self.nb * x.H * x.W * lay.cin)
                                   + 4 * slabs * lay.cout_p * ntap * x.c))
         self.bwd.append(o)
-        o = self._op(L.OP_WREDUCE)
-        r = o.u.wreduce
-        r.ws, r.dw, r.cmap = 0, 0, lay.cmap_t.data_ptr()
-        r.splits, r.ws_rows, r.ws_k, r.co_off = slabs, lay.cout_p, ntap * x.c, 0
-        r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, lay.cin, lay.kh, lay.kw, x.c
-        first = lay not in self.wg_first
-        r.beta = 0 if first else 1
-        o.meta = _reduce_meta(lay.name, r)
-        self.bwd.append(o)
-        self._grad_slots.append((len(self.bwd) - 1, lay, "weight", first))
+        self._reduce_op(lay, "weight", slabs, ntap * x.c, x.c)
         if lay.has_bias:
-            o = self._op(L.OP_WREDUCE)
-            r = o.u.wreduce
-            r.ws, r.dw, r.cmap = 0, 0, None
-            r.splits, r.ws_rows, r.ws_k, r.co_off = bslabs, lay.cout_p, 1, 0
-            r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, 1, 1, 1, 1
-            r.beta = 0 if first else 1
-            o.meta = _reduce_meta(lay.name + ".bias", r)
-            o.ws_off = wfl
-            self.bwd.append(o)
-            self._grad_slots.append((len(self.bwd) - 1, lay, "bias", first))
-        self.wg_first[lay] = True
-        self._uses_left[lay] -= 1
-        if self._uses_left[lay] == 0:
-            self.completions.append((len(self.bwd), lay))
+            self._reduce_op(lay, "bias", bslabs, ws_off=o.bws_off)
+        self._close_layer(lay)
 
     def _im2col_dgrad(self, lay, x, phases):
         """Narrow-input stride-1 data gradients (HRNet's 3x3 448->3 / 448->20 heads: the
@@ -1833,16 +1816,15 @@ class Plan:
         return (ph["th"] * ph["tw"] > 1 and lay.cout_p % 8 == 0 and lay.cout_p <= 32 and x.c >= 128
                 and kpad % 64 == 0 and ph["ry"] == 0 and ph["rx"] == 0)
 
-    def _im2col_dgrad_ops(self, lay, x, xg, out, gout, gld, phase, res, res_ld, z, z_ld, dact, beta):
+    def _im2col_dgrad_ops(self, lay, x, xg, out, gout, gld, phase, epi):
         ph, wt, kpad = phase
         nb = self.nb
         npx = nb * ph["oh"] * ph["ow"]
         # one scratch shared by the layers (in order on the data lane)
-        buf = self.__dict__.get("_i2c")
-        if buf is None or buf.numel() < npx * kpad:
-            buf = torch.empty(npx * kpad, dtype=self.dtype, device=self.device)
-            self._i2c = buf
-            self.keep.append(buf)
+        if self._i2c is None or self._i2c.numel() < npx * kpad:
+            self._i2c = torch.empty(npx * kpad, dtype=self.dtype, device=self.device)
+            self.keep.append(self._i2c)
+        buf = self._i2c
         e = self.ew_desc(L.EW_IM2COL, nb, out.H, out.W, kpad, buf.data_ptr(), kpad,
                          srcs=[(gout, gld, ph["th"], ph["tw"]), (None, 0, ph["dy0"], ph["dx0"]),
                                (None, 0, ph["ddy"], ph["ddx"])])
@@ -1851,11 +1833,11 @@ class Plan:
                       bytes=float(self.es * npx * (lay.cout_p + kpad)))
         one = dict(th=1, tw=1, dy0=0, dx0=0, ddy=1, ddx=1)
         o = self.conv_desc(buf.data_ptr(), kpad, nb, out.H, out.W, kpad, wt.data_ptr(), kpad, x.c, ph["oh"], ph["ow"],
-                           1, 1, one, xg, x.buf.C, x.H, x.W, res=res, res_ld=res_ld, z=z, z_ld=z_ld, dact=dact,
-                           beta=beta)
+                           1, 1, one, xg, x.buf.C, x.H, x.W, **epi._asdict())
         o.meta = dict(cls="conv_dgrad", name=lay.name, flops=2.0 * npx * lay.cin * lay.cout * ph["th"] * ph["tw"],
-                      bytes=float(self.es * (npx * kpad + npx * lay.cin * (1 + (res is not None) + (z is not None)
-                                                                            + beta) + lay.cout * lay.cin * 9)))
+                      bytes=float(self.es * (npx * kpad + npx * lay.cin * (1 + (epi.res is not None)
+                                                                            + (epi.z is not None) + epi.beta)
+                                             + lay.cout * lay.cin * 9)))
         return [e, o]
 
     def _convT_backward(self, op, gout, gld):
@@ -1868,69 +1850,37 @@ class Plan:
         nb = self.nb
         taps = lay.fwd_taps()
         ntap = lay.kh * lay.kw
+        npix = nb * x.H * x.W
         if lay.trainable:
-            npix = nb * x.H * x.W
-            tiles = rup(lay.cout_p, 64) // 64 * (rup(out.c, 64) // 64)
-            bkp = 64 if self.dtype == torch.bfloat16 else 32
-            splits = max(1, min(max(1, npix // (bkp * 4)), 1024 // max(1, tiles * ntap)))
-            o = self._op(L.OP_WGRAD)
-            d = o.u.wgrad
-            d.g, d.x, d.ws = self.ptr(x), gout, 0
-            d.g_ld, d.x_ld = x.buf.C, gld
-            d.n, d.oh, d.ow, d.cout = nb, x.H, x.W, lay.cout_p
-            d.ih, d.iw, d.c, d.sy, d.sx = out.H, out.W, out.c, lay.stride, lay.stride
-            d.th, d.tw, d.dy0, d.dx0, d.ddy, d.ddx = taps["th"], taps["tw"], taps["dy0"], taps["dx0"], 1, 1
-            d.dtype = self.dt
-            lib = L.load()
-            hint = lib.dvie_wgrad_splits_hint(ctypes.byref(d))
-            d.splits = hint if hint > 0 else splits
-            slabs = lib.dvie_wgrad_slabs(ctypes.byref(d))
-            self.ws_floats = max(self.ws_floats, slabs * lay.cout_p * ntap * out.c)
+            o, slabs, _ = self._wgrad_op(self.ptr(x), x.buf.C, gout, gld, x.H, x.W, lay.cout_p, out.H, out.W, out.c,
+                                         lay.stride, taps)
             o.meta = dict(cls="conv_wgrad", name=lay.name, flops=2.0 * npix * lay.cout * lay.cin * ntap,
                           bytes=float(self.es * (npix * lay.cout + nb * out.H * out.W * lay.cin)))
             self.bwd.append(o)
-            o = self._op(L.OP_WREDUCE)
-            r = o.u.wreduce
-            r.ws, r.dw, r.cmap = 0, 0, lay.cmap_t.data_ptr()
-            r.splits, r.ws_rows, r.ws_k, r.co_off = slabs, lay.cout_p, ntap * out.c, 0
-            r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cout, lay.cin, lay.kh, lay.kw, out.c
-            first = lay not in self.wg_first
-            r.beta = 0 if first else 1
-            self.bwd.append(o)
-            self._grad_slots.append((len(self.bwd) - 1, lay, "weight", first))
+            self._reduce_op(lay, "weight", slabs, ntap * out.c, out.c)
             if lay.has_bias:
-                opix = nb * out.H * out.W
-                csplits = max(1, min(2048, opix // 512))
-                o = self._op(L.OP_COLSUM)
-                cd = o.u.colsum
-                cd.g, cd.ws, cd.g_ld, cd.rows, cd.c, cd.splits, cd.dtype = gout, 0, gld, opix, out.c, csplits, self.dt
-                self.ws_floats = max(self.ws_floats, csplits * out.c)
-                self.bwd.append(o)
-                o = self._op(L.OP_WREDUCE)
-                r = o.u.wreduce
-                r.ws, r.dw, r.cmap = 0, 0, None
-                r.splits, r.ws_rows, r.ws_k, r.co_off = csplits, out.c, 1, 0
-                r.cout_p, r.cin_p, r.kh_n, r.kw_n, r.c = lay.cin, 1, 1, 1, 1
-                r.beta = 0 if first else 1
-                self.bwd.append(o)
-                self._grad_slots.append((len(self.bwd) - 1, lay, "bias", first))
-            self.wg_first[lay] = True
-            self._uses_left[lay] -= 1
-            if self._uses_left[lay] == 0:
-                self.completions.append((len(self.bwd), lay))
-        if x.buf.needs_grad:
-            xg = self.ptr(x, grad=True)
+                self._reduce_op(lay, "bias", self._colsum_op(gout, gld, nb * out.H * out.W, out.c))
+            self._close_layer(lay)
+        if not x.buf.needs_grad:
+            return
 
-            def em(beta, res, res_ld, dact, z, z_ld, lay=lay, x=x, xg=xg, out=out, gout=gout, gld=gld):
-                o = self.conv_desc(gout, gld, nb, out.H, out.W, out.c, lay.wf.data_ptr(), lay.kpad, lay.cout_p,
-                                   x.H, x.W, lay.stride, lay.stride, taps, xg, x.buf.C, x.H, x.W,
-                                   res=res, res_ld=res_ld, z=z, z_ld=z_ld, dact=dact, beta=beta)
-                npx = nb * x.H * x.W
-                o.meta = dict(cls="conv_dgrad", name=lay.name, flops=2.0 * npx * lay.cout * lay.cin * ntap,
-                              bytes=float(self.es * (nb * out.H * out.W * lay.cin + npx * lay.cout)))
-                return [o]
+        def em(epi):
+            o = self.conv_desc(gout, gld, nb, out.H, out.W, out.c, lay.wf.data_ptr(), lay.kpad, lay.cout_p,
+                               x.H, x.W, lay.stride, lay.stride, taps, self.ptr(x, grad=True), x.buf.C, x.H, x.W,
+                               **epi._asdict())
+            o.meta = dict(cls="conv_dgrad", name=lay.name, flops=2.0 * npix * lay.cout * lay.cin * ntap,
+                          bytes=float(self.es * (nb * out.H * out.W * lay.cin + npix * lay.cout)))
+            return [o]
 
-            self._contrib(x, em)
+        self._contrib(x, em)
+
+    # graph op type -> its lowering, per direction
+    _FWD = {LabelInputOp: _label_input_fwd, InputOp: _input_fwd, ConvOp: _conv_fwd, ConvTOp: _convT_fwd,
+            AttnOp: _attn_fwd, FuseOp: _fuse_fwd, MaskOp: _mask_fwd, OutNCHWOp: _out_nchw_fwd, PoolOp: _pool_fwd,
+            BNOp: _bn_fwd, HeadOp: _head_fwd, L1FeatOp: _l1feat_fwd}
+    _BWD = {LabelInputOp: _input_backward, InputOp: _input_backward, ConvOp: _conv_backward, ConvTOp: _convT_backward,
+            AttnOp: _attn_backward, FuseOp: _fuse_backward, MaskOp: _mask_backward, OutNCHWOp: _out_nchw_backward,
+            PoolOp: _pool_backward, BNOp: _bn_backward, HeadOp: _head_backward, L1FeatOp: _l1feat_backward}
 
     # ---------------- finalize ----------------
     def _batch_reductions(self):
@@ -1955,13 +1905,12 @@ class Plan:
                 writer_of[i] = cur
             elif o.kind == L.OP_WREDUCE:
                 had_reduce = True
-                if getattr(o, "ws_ptr", None) is None:
+                if o.ws_ptr is None:
                     r = o.u.wreduce
                     writer_of[i] = cur
-                    size[cur] = max(size.get(cur, 0), getattr(o, "ws_off", 0) + r.splits * r.ws_rows * r.ws_k)
+                    size[cur] = max(size.get(cur, 0), o.ws_off + r.splits * r.ws_rows * r.ws_k)
         # pass 2: batches, regions, the multi ops
         new, remap, pending, base, off, live_end = [], {}, [], {}, 0, 0
-        self._multi = []  # (host descriptor array, [(ws_ptr or None, float offset in self.ws)])
 
         def flush():
             nonlocal pending, off
@@ -1971,8 +1920,7 @@ class Plan:
             wsrc = []
             for j, (oi, o) in enumerate(pending):
                 arr[j] = o.u.wreduce
-                wp = getattr(o, "ws_ptr", None)
-                wsrc.append((wp, None if wp else base[writer_of[oi]] + getattr(o, "ws_off", 0)))
+                wsrc.append((o.ws_ptr, None if o.ws_ptr else base[writer_of[oi]] + o.ws_off))
             m = self._op(L.OP_WREDUCE_MULTI)
             m.u.wreduce_multi.descs = ctypes.addressof(arr)
             m.u.wreduce_multi.n = len(pending)
@@ -2018,12 +1966,10 @@ class Plan:
         self.completions = [(remap[idx - 1] + 1, lay) for idx, lay in self.completions]
         # backward indices recorded while building: moved with their ops
         self.ext_ograd = {k: remap[i] for k, i in self.ext_ograd.items()}
-        if hasattr(self, "ext_head_grad"):
-            self.ext_head_grad = {k: remap[i] for k, i in self.ext_head_grad.items()}
+        self.ext_head_grad = {k: remap[i] for k, i in self.ext_head_grad.items()}
         self.ext_grad = {k: [(remap[i], op) for i, op in v] for k, v in self.ext_grad.items()}
-        if hasattr(self, "ext_mask"):
-            self.ext_mask = {k: [(w, remap[i] if w == "bwd" else i, op) for w, i, op in v]
-                             for k, v in self.ext_mask.items()}
+        self.ext_mask = {k: [(w, remap[i] if w == "bwd" else i, op) for w, i, op in v]
+                         for k, v in self.ext_mask.items()}
         slots = []
         pos = {}  # multi op index -> the old indices of its reductions, in order
         for oi, ni in sorted(remap.items()):
@@ -2036,7 +1982,6 @@ class Plan:
             else:
                 slots.append((remap[idx], lay, which, first))
         self._grad_slots = slots
-        self.n_bwd = len(self.bwd)
 
     def _wreduce_desc(self, idx):
         """the dvie_wreduce_desc of a gradient slot (one reduction op, or an element of a
@@ -2064,24 +2009,25 @@ class Plan:
             if o.kind in (L.OP_WGRAD, L.OP_WREDUCE, L.OP_COLSUM, L.OP_WREDUCE_MULTI) and wlane:
                 o.lane = 1
             if o.kind == L.OP_WGRAD:
-                o.u.wgrad.ws = wsp + 4 * getattr(o, "ws_base", 0)
-                if hasattr(o, "bws_off"):  # bias partials after the weight slabs
-                    o.u.wgrad.bws = wsp + 4 * (getattr(o, "ws_base", 0) + o.bws_off)
+                o.u.wgrad.ws = wsp + 4 * o.ws_base
+                if o.bws_off is not None:  # bias partials after the weight slabs
+                    o.u.wgrad.bws = wsp + 4 * (o.ws_base + o.bws_off)
             elif o.kind == L.OP_COLSUM:
-                o.u.colsum.ws = wsp + 4 * getattr(o, "ws_base", 0)
+                o.u.colsum.ws = wsp + 4 * o.ws_base
             elif o.kind == L.OP_WREDUCE:
-                o.u.wreduce.ws = getattr(o, "ws_ptr", None) or wsp + 4 * getattr(o, "ws_off", 0)
-        for arr, wsrc in getattr(self, "_multi", []):
+                o.u.wreduce.ws = o.ws_ptr or wsp + 4 * o.ws_off
+        for arr, wsrc in self._multi:
             for j, (wp, off) in enumerate(wsrc):
                 arr[j].ws = wp if wp else wsp + 4 * off
             self.keep.append(arr)
+        self._l1_bwd = [(i, o.l1_seed) for i, o in enumerate(self.bwd) if o.l1_seed is not None]
+        self.bwd_arr = (L.Op * max(1, len(self.bwd)))(*self.bwd) if self.bwd else None
+        self.n_bwd = len(self.bwd)
         # pack op (all layers, one launch) goes first in the forward list
         descs = self._pack_descs
         if not descs:  # no convolutions (e.g. a pointwise-only plan)
             self.fwd_arr = (L.Op * max(1, len(self.fwd)))(*self.fwd)
             self.fwd_off = 0
-            self.bwd_arr = (L.Op * max(1, len(self.bwd)))(*self.bwd) if self.bwd else None
-            self.n_bwd = len(self.bwd)
             return
         blk = 0  # flat grid: each descriptor's first block (csrc/conv.hip pack_kernel)
         for d in descs:
@@ -2097,10 +2043,15 @@ class Plan:
         po.u.pack.blocks = blk
         self.fwd_arr = (L.Op * (len(self.fwd) + 1))(po, *self.fwd)
         self.fwd_off = 1
-        self.bwd_arr = (L.Op * max(1, len(self.bwd)))(*self.bwd) if self.bwd else None
-        self.n_bwd = len(self.bwd)
 
     # ---------------- execution ----------------
+    @staticmethod
+    def _point_at(d, t, c0=0):
+        """point the external operand of a pointwise descriptor at a logical-NCHW fp32
+        tensor of any strides, from its channel c0 on"""
+        d.sn, d.sc, d.sh, d.sw = t.stride()
+        d.ext = t.data_ptr() + 4 * c0 * d.sc
+
     def set_input_labels(self, key, parts):
         """Patch the label-map input `key` (Graph.input_labels): parts[k] is frame k's uint8
         (n, H, W) tensor (any strides), read in place."""
@@ -2127,9 +2078,7 @@ class Plan:
             d = self.fwd_arr[idx + self.fwd_off].u.ew
             assert t.shape[0] == self._part(op.part)[1], (key, tuple(t.shape), self.nf)
             assert t.shape[2:] == (op.out.H, op.out.W) and t.shape[1] >= op.ext_c0 + op.ext_c, (key, tuple(t.shape))
-            sn, sc, sh, sw = t.stride()
-            d.ext = t.data_ptr() + 4 * op.ext_c0 * sc
-            d.sn, d.sc, d.sh, d.sw = sn, sc, sh, sw
+            self._point_at(d, t, op.ext_c0)
             d.src1, d.sh1 = None, 0
 
     def set_input_parts(self, key, parts):
@@ -2147,9 +2096,7 @@ class Plan:
             j = max(i for i in range(len(parts)) if starts[i] <= op.ext_c0)
             t = parts[j]
             assert t.shape[0] == self._part(op.part)[1] and t.shape[2:] == (op.out.H, op.out.W), (key, tuple(t.shape))
-            sn, sc, sh, sw = t.stride()
-            d.ext = t.data_ptr() + 4 * (op.ext_c0 - starts[j]) * sc
-            d.sn, d.sc, d.sh, d.sw = sn, sc, sh, sw
+            self._point_at(d, t, op.ext_c0 - starts[j])
             end = op.ext_c0 + op.ext_c
             if end > starts[j + 1]:  # the op's channels continue in the next block
                 assert j + 1 < len(parts) and end <= starts[j + 2], (key, op.ext_c0, op.ext_c, starts)
@@ -2166,19 +2113,13 @@ class Plan:
     def set_mask(self, key, t):
         """Patch the external NCHW fp32 mask `key` (channel op.chan of t) into its ops."""
         assert t.dtype == torch.float32 and t.device.type == self.device.type
-        sn, sc, sh, sw = t.stride()
-        for where, idx, op in getattr(self, "ext_mask", {}).get(key, []):
-            d = (self.fwd_arr[idx + self.fwd_off] if where == "fwd" else self.bwd_arr[idx]).u.ew
-            d.ext = t.data_ptr() + 4 * op.chan * sc
-            d.sn, d.sc, d.sh, d.sw = sn, sc, sh, sw
+        for where, idx, op in self.ext_mask.get(key, []):
+            self._point_at((self.fwd_arr[idx + self.fwd_off] if where == "fwd" else self.bwd_arr[idx]).u.ew, t, op.chan)
 
     def set_output_nchw(self, key, t):
         """Point the NCHW sink `key` at an fp32 tensor (any strides)."""
         assert t.dtype == torch.float32
-        d = self.fwd_arr[self.ext_nchw_out[key] + self.fwd_off].u.ew
-        sn, sc, sh, sw = t.stride()
-        d.ext = t.data_ptr()
-        d.sn, d.sc, d.sh, d.sw = sn, sc, sh, sw
+        self._point_at(self.fwd_arr[self.ext_nchw_out[key] + self.fwd_off].u.ew, t)
 
     def set_head_output(self, key, t):
         """Point head `key` at an fp32 vector of length n*(h/pool)*(w/pool)."""
@@ -2195,10 +2136,7 @@ class Plan:
     def set_output_grad(self, key, t):
         """Patch the incoming gradient (fp32, any strides, logical NCHW) of output `key`."""
         assert t.dtype == torch.float32
-        d = self.bwd_arr[self.ext_ograd[key]].u.ew
-        sn, sc, sh, sw = t.stride()
-        d.ext = t.data_ptr()
-        d.sn, d.sc, d.sh, d.sw = sn, sc, sh, sw
+        self._point_at(self.bwd_arr[self.ext_ograd[key]].u.ew, t)
 
     def set_l1_loss(self, out=None, value_scale=1.0, grad_scale=1.0):
         """Where the VGG feature-L1 loss ops put their values, and the gradient scale.
@@ -2213,18 +2151,13 @@ class Plan:
                 d.out, d.out_acc, d.out_scale = self.l1_out.data_ptr() + 4 * lev, 0, 1.0
             else:
                 d.out, d.out_acc, d.out_scale = out.data_ptr(), int(k > 0), value_scale / nl
-        if self.bwd_arr is not None:
-            if not hasattr(self, "_l1_bwd"):
-                self._l1_bwd = [(i, o.l1_seed) for i, o in enumerate(self.bwd) if hasattr(o, "l1_seed")]
-            for i, base in self._l1_bwd:
-                self.bwd_arr[i].u.ew.scale = base * grad_scale
+        for i, base in self._l1_bwd:
+            self.bwd_arr[i].u.ew.scale = base * grad_scale
 
     def set_input_grad(self, key, t, accumulate=False):
         for idx, op in self.ext_grad[key]:
             d = self.bwd_arr[idx].u.ew
-            sn, sc, sh, sw = t.stride()
-            d.ext = t.data_ptr() + 4 * op.ext_c0 * sc
-            d.sn, d.sc, d.sh, d.sw = sn, sc, sh, sw
+            self._point_at(d, t, op.ext_c0)
             d.beta = int(accumulate)
 
     def set_param_grads(self, accumulate=False, fresh=()):
@@ -2273,8 +2206,8 @@ class Plan:
         padded channels included, the caller slices the real ones)."""
         out = []
         for op in self.g.ops:
-            r = getattr(op, "out", None)
-            if r is None or getattr(op, "act", 0) not in (L.ACT_LRELU, L.ACT_RELU) or r.buf.t is None:
+            r = op.out
+            if r is None or op.act not in (L.ACT_LRELU, L.ACT_RELU) or r.buf.t is None:
                 continue
             out.append((r.buf.t[..., r.c0:r.c0 + r.c] > 0).permute(0, 3, 1, 2).cpu())
         return out

@@ -236,6 +236,29 @@ def test_fused_segenc_backward_leaves_no_dead_work():
             assert o.u.ew.dact != L.ACT_ELU, "an ELU derivative pass is left in the backward"
 
 
+def test_setters_on_a_plan_without_their_ops():
+    """A forward plan of one conv has no mask, head, NCHW sink or feature-L1 op; its maps of
+    such ops exist and are empty: set_mask on an unknown key patches nothing, the setters
+    that need their op raise KeyError, and set_l1_loss has nothing to rescale."""
+    conv = torch.nn.Conv2d(5, 12, 3, padding=1)
+    g = E.Graph(torch.float32)
+    x, y = g.buffer("x", 8, 16, 8), g.buffer("y", 8, 16, 16)
+    g.input_nchw(E.R(x), "x", ext_c=5)
+    g.conv(E.R(x), conv, E.R(y), name="conv")
+    plan = g.compile(2, torch.device("cpu"), backward=False)
+    assert plan.n_bwd == 0 and plan.bwd_arr is None
+    t = torch.zeros(2, 1, 8, 16)
+    before = bytes(plan.fwd_arr)
+    plan.set_mask("fg", t)
+    assert bytes(plan.fwd_arr) == before
+    for setter in (plan.set_output_nchw, plan.set_head_output, plan.set_head_grad):
+        with pytest.raises(KeyError):
+            setter("nothing", t)
+    plan.set_l1_loss()
+    plan.set_l1_loss(out=torch.zeros(1), value_scale=2.0, grad_scale=0.5)
+    assert bytes(plan.fwd_arr) == before
+
+
 def test_pack_blocks_from_the_library():
     """The flat pack grid's per-descriptor block counts come from the library
     (dvie_pack_blocks), and the descriptors' blk0 tile the grid."""
