@@ -43,6 +43,7 @@ class ConvDesc(ctypes.Structure):
         ("yh", i32), ("yw", i32), ("osy", i32), ("osx", i32), ("ory", i32), ("orx", i32),
         ("act", i32), ("dact", i32), ("beta", i32), ("dtype", i32),
         ("out_f32", i32), ("alpha", f32), ("phc", i32), ("pad1", i32),
+        ("zbits", vp), ("zbits_ld", i64),
     ]
 
 
@@ -286,7 +287,7 @@ EXPORTS = [
     "dvie_adam_dev", "dvie_mfma_probe", "dvie_launch_probe", "dvie_sum_f32", "dvie_wgrad_bias_slabs", "dvie_head3_bwd",
     "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_pack_blocks", "dvie_trace_kernels", "dvie_traced_kernels",
     "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_score_ws_bytes",
-    "dvie_synth_load_pad", "dvie_synth_finish_crop",
+    "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits",
 ]
 
 _lib = None
@@ -332,7 +333,8 @@ def load():
         lib.dvie_trace_kernels.restype = i32
         lib.dvie_traced_kernels.argtypes = []
         lib.dvie_traced_kernels.restype = ctypes.c_char_p
-        for name in ("dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_bn_partial_splits", "dvie_pack_blocks"):
+        for name in ("dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_bn_partial_splits", "dvie_pack_blocks",
+                     "dvie_conv_zbits"):
             getattr(lib, name).argtypes = [vp]
             getattr(lib, name).restype = i32
         lib.dvie_run_ops.argtypes = [vp, i32, vp]

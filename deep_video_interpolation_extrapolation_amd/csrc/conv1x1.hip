@@ -80,6 +80,15 @@ struct G1Cfg {
 // PRE (bf16 output, single K-step only): epilogue operands loaded into registers right after
 // the stage's DMA, so their HBM latency overlaps the operand DMA instead of following the
 // MFMAs (1 residual, 2 accumulate target, 4 activation input).
+// PRE bit 8 (with bit 4, LRELU / RELU derivative, 128-channel wave tiles): the activation input
+// comes from the sign bitmap (dvie_conv_desc.zbits): one 16-byte load per lane covers the 128
+// channels of its pixel, in place of eight 16-byte loads of z.
+// PRE bit 16 (a forward with ReLU / LeakyReLU: no bits 2, 4; 128- and 64-channel wave tiles):
+// the launch also writes the sign bitmap p.zbits.  The lane's 2 TMC bytes are at positions
+// 4j + 2P + h of its pixel's 4 TMC, so a permlane32 swap with the other half leaves each lane
+// with 2 TMC contiguous bytes, stored as one 8-byte (dword) vector store.  A variant of its
+// own: as a run-time branch of the plain forward the bitmap code cost that kernel 10-13 VGPRs
+// and, with a residual, an occupancy step (121 -> 134).
 // CE (bf16 output, MI = 1, 8 accumulator chunks per lane, identity placement, full channel
 // tiles): the packed outputs are transposed across each 8-lane group (three xor-shuffle
 // stages), so store instruction k writes 4 whole pixels x 256 B instead of 32 pixels x 32 B.
@@ -181,12 +190,28 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_kernel(const dvie_conv
   // epilogue-operand prefetch (PRE): lane (pixel wp*32*MI + 32*i + r32, channels
   // c0 + wc*32*TMC + 32*j + 16*P + 8*h .. +7); identity output placement only (checked at launch)
   static_assert(PRE == 0 || (NS == 1 && !OUTF32), "operand prefetch: single K-step, bf16 output");
-  i32x4 pr_r[(PRE & 1) ? MI : 1][TMC][2], pr_b[(PRE & 2) ? MI : 1][TMC][2], pr_z[(PRE & 4) ? MI : 1][TMC][2];
+  constexpr bool ZPROD = (PRE & 16) != 0;  // writes the bitmap
+  static_assert(!ZPROD || ((TMC == 4 || TMC == 2) && MI == 1 && (PRE & 14) == 0), "bitmap writer: a forward");
+  constexpr bool ZB = (PRE & 8) != 0;  // activation input from the sign bitmap
+  static_assert(!ZB || ((PRE & 4) != 0 && TMC == 4), "bitmap operand: 16 bytes per 128-channel wave tile");
+  i32x4 pr_r[(PRE & 1) ? MI : 1][TMC][2], pr_b[(PRE & 2) ? MI : 1][TMC][2], pr_z[((PRE & 4) && !ZB) ? MI : 1][TMC][2];
+  i32x4 pr_zb[ZB ? MI : 1];
+  if constexpr (ZB) {  // the 16 bitmap bytes of the lane's pixel(s): channels c0 + wc*128 .. +127
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const int pix = p0 + (wave % NWP) * 32 * MI + 32 * i + r32;
+      const long long q = pix < npix ? pix : 0;
+      pr_zb[i] = *(const i32x4*)((const char*)p.zbits + q * p.zbits_ld + ((c0 + (wave / NWP) * 32 * TMC) >> 3));
+    }
+  }
   // CE tiles with two or more operands (layer1's 256-channel data gradients: residual +
   // activation input) load them row-coalesced: 0.47 -> 0.43 ms each; with a single operand
   // the transposes' extra registers cost an occupancy step (121 -> 148 VGPRs) and the
   // forward with a residual measured 0.247 -> 0.290 ms (profiles/r05l/)
-  constexpr bool CEL = CE && (PRE & (PRE - 1)) != 0;
+  // (an activation input that comes from the bitmap is no 16-byte operand stream: with it,
+  // residual + derivative counts as a single operand)
+  constexpr int STREAMS = (PRE & 3) | (ZB ? 0 : (PRE & 4));
+  constexpr bool CEL = CE && (STREAMS & (STREAMS - 1)) != 0;
   if constexpr (CEL) {
     // CE tiles: the operands are loaded in the transposed layout of the CE stores -- lane
     // (h, 8 a + b), chunk k = pixel 8 a + k, channels 16 b + 8 h of the wave's 128 -- so each
@@ -204,10 +229,10 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_kernel(const dvie_conv
         pr_r[0][k >> 1][k & 1] = ok ? *(const i32x4*)((const bf16_t*)p.res + q * p.res_ld + co) : i32x4{0, 0, 0, 0};
       if constexpr ((PRE & 2) != 0)
         pr_b[0][k >> 1][k & 1] = ok ? *(const i32x4*)((const bf16_t*)p.y + q * p.y_ld + co) : i32x4{0, 0, 0, 0};
-      if constexpr ((PRE & 4) != 0)
+      if constexpr ((PRE & 4) != 0 && !ZB)
         pr_z[0][k >> 1][k & 1] = ok ? *(const i32x4*)((const bf16_t*)p.z + q * p.z_ld + co) : i32x4{0, 0, 0, 0};
     }
-  } else if constexpr (PRE != 0) {
+  } else if constexpr ((PRE & 7) != 0) {
     const int wp0 = wave % NWP, wc0 = wave / NWP;
 #pragma unroll
     for (int i = 0; i < MI; ++i)
@@ -223,7 +248,7 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_kernel(const dvie_conv
             pr_r[i][j][P] = ok ? *(const i32x4*)((const bf16_t*)p.res + q * p.res_ld + co) : i32x4{0, 0, 0, 0};
           if constexpr ((PRE & 2) != 0)
             pr_b[i][j][P] = ok ? *(const i32x4*)((const bf16_t*)p.y + q * p.y_ld + co) : i32x4{0, 0, 0, 0};
-          if constexpr ((PRE & 4) != 0)
+          if constexpr ((PRE & 4) != 0 && !ZB)
             pr_z[i][j][P] = ok ? *(const i32x4*)((const bf16_t*)p.z + q * p.z_ld + co) : i32x4{0, 0, 0, 0};
         }
   }
@@ -285,11 +310,12 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_kernel(const dvie_conv
     };
     if constexpr ((PRE & 1) != 0) tr(pr_r[0]);
     if constexpr ((PRE & 2) != 0) tr(pr_b[0]);
-    if constexpr ((PRE & 4) != 0) tr(pr_z[0]);
+    if constexpr ((PRE & 4) != 0 && !ZB) tr(pr_z[0]);
   }
   i32x4 ob[CE ? 8 : 1];
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
+  unsigned zq[2] = {0u, 0u};  // the lane's bitmap bytes: chunk k = 2j + P in byte k & 3 of zq[k >> 2]
   const int pix0 = p0 + wp * 32 * MI + 32 * i + r32;
   const int pix = CE ? min(pix0, npix - 1) : pix0;  // (CE: every lane takes part in the shuffles)
   float v[TMC][2][8];
@@ -329,18 +355,49 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_kernel(const dvie_conv
         }
         act8(w, p.act, p.alpha);
         if (p.dact) {
-          if constexpr ((PRE & 4) != 0)
+          if constexpr (ZB)  // byte 4j + 2P + h of the pixel's 16
+            dact_bits8(w, ((unsigned)pr_zb[i][j] >> (8 * (2 * P + hh))) & 0xffu, p.dact, p.alpha);
+          else if constexpr ((PRE & 4) != 0)
             dact_bf16x8(w, pr_z[i][j][P], p.dact, p.alpha);
           else
             dact_bf16x8(w, *(const i32x4*)((const bf16_t*)p.z + yp * p.z_ld + co), p.dact, p.alpha);
         }
         const i32x4 o = pack_bf16x8(w);
+        // (CE keeps the packed chunks: their bits are taken after the loop, when the fp32
+        // values are dead -- inside it they cost the 128-VGPR occupancy step)
+        if constexpr (ZPROD && !CE) zq[(2 * j + P) / TMC] |= sign_bits8(o) << (8 * ((2 * j + P) % TMC));
         if constexpr (CE)
           ob[2 * j + P] = o;
         else if (!(dbg & 1) || w[0] == 12345.678f)
           *(i32x4*)dst = o;
       }
     }
+  if constexpr (ZPROD) {
+    if constexpr (CE) {
+#pragma unroll
+      for (int k = 0; k < 2 * TMC; ++k) zq[k / TMC] |= sign_bits8(ob[k]) << (8 * (k % TMC));
+    }
+    {
+      // half h keeps bytes 2 TMC h .. + 2 TMC - 1 of the pixel's 4 TMC (TMC = 4: 8 of 16, one
+      // 8-byte store; TMC = 2: 4 of 8, a dword store): the swap hands it their even-position
+      // bytes (from half 0) in sw[0] and the odd-position ones (from half 1) in sw[1]
+      const auto sw = __builtin_amdgcn_permlane32_swap(zq[0], zq[1], false, false);
+      const unsigned ev = sw[0], od = sw[1];
+      const unsigned z0 = (ev & 0xffu) | ((od & 0xffu) << 8) | ((ev & 0xff00u) << 8) | ((od & 0xff00u) << 16);
+      const int cz = c0 + wc * 32 * TMC + 16 * TMC * hh;  // (cout % (16 TMC) == 0: a half's span is whole or absent)
+      char* zdst = (char*)p.zbits + yp * p.zbits_ld + (cz >> 3);
+      if (pix0 < npix && cz < p.cout) {
+        if constexpr (TMC == 4) {
+          i32x2 zo;
+          zo[0] = (int)z0;
+          zo[1] = (int)(((ev >> 16) & 0xffu) | ((od >> 8) & 0xff00u) | ((ev >> 8) & 0xff0000u) | (od & 0xff000000u));
+          *(i32x2*)zdst = zo;
+        } else {
+          *(unsigned*)zdst = z0;
+        }
+      }
+    }
+  }
   }
   if constexpr (CE) {
     transpose8x8(ob, lane);
@@ -526,7 +583,10 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_persist_kernel(const d
 // placement) reads no memory.
 // AB: timing-only ablations (instantiated in -DDVIE_TIMING_DBG builds only; DVIE_1X1_DBG):
 // 1 no stores, 2 no MFMAs, 4 no DMA after the prologue
-template <int TMC, int NWP, int MI, int NWC, int ACT, int AB = 0>
+// ZW (ACT = LeakyReLU): the epilogue also writes the sign bitmap p.zbits, as conv1x1_kernel's
+// PRE bit 16 does: per pixel block one more uniform buffer store (8 bytes: the half wave's 64
+// channels of the lane's pixel), counted by the wait after the epilogue.
+template <int TMC, int NWP, int MI, int NWC, int ACT, int AB = 0, bool ZW = false>
 __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_ring_kernel(const dvie_conv_desc p, int n_ct, int n_tiles) {
   constexpr int dbg = AB;
   typedef G1Cfg<TMC, 2, 64, NWP, MI, NWC> C;
@@ -560,6 +620,10 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_ring_kernel(const dvie
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)ybytes, 0x00020000);
   // (no bias: a zero-length range, every load returns zeros)
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, p.bias ? p.cout * 4 : 0, 0x00020000);
+  static_assert(!ZW || (TMC == 4 && ACT == DVIE_ACT_LRELU), "bitmap writer: 16 bytes per 128-channel wave tile");
+  const __amdgpu_buffer_rsrc_t rzb = __builtin_amdgcn_make_buffer_rsrc(
+      ZW ? p.zbits : nullptr, 0,
+      ZW ? (int)(((unsigned long long)p.n * p.yh * p.yw - 1) * (unsigned long long)p.zbits_ld + p.cout / 8) : 0, 0x00020000);
 
   // per-lane DMA geometry, once: piece q row (the same for both operands) and its byte offset
   // within a row block (channel chunk swizzled); the per-issue part is wave-uniform
@@ -642,7 +706,7 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_ring_kernel(const dvie
     // barrier); only 2 jj + 2 -- plus the previous tile's epilogue stores -- may be in flight;
     // every wave's reads of job jj - 1's slots are done (lgkmcnt 0)
     if (after_epi)
-      DVIE_VMCNT1(PPH + 2 * MI * TMC);
+      DVIE_VMCNT1(PPH + 2 * MI * TMC + (ZW ? MI : 0));
     else
       DVIE_VMCNT1(PPH);
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
@@ -714,6 +778,7 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_ring_kernel(const dvie
         const int oy = r / p.ow, ox = r - oy * p.ow;
         yp = ((long long)n * p.yh + oy * p.osy + p.ory) * p.yw + ox * p.osx + p.orx;
       }
+      unsigned zq[2] = {0u, 0u};  // (ZW) chunk k = 2j + P in byte k & 3 of zq[k >> 2]
 #pragma unroll
       for (int j = 0; j < TMC; ++j)
 #pragma unroll
@@ -731,12 +796,25 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_ring_kernel(const dvie
             for (int e = 0; e < 8; ++e) w[e] = fmaxf(w[e], w[e] * p.alpha);  // (0 <= alpha <= 1: launch)
           }
           const i32x4 o = pack_bf16x8(w);
+          if constexpr (ZW) zq[j >> 1] |= sign_bits8(o) << (8 * (2 * (j & 1) + P));
           const int co = c0 + wc * 32 * TMC + 32 * j + 16 * P + 8 * hh;
           // (a buffer store that every wave issues, out-of-range lanes aimed past the buffer's
           // range and dropped: the per-wave store count the next wait counts on is uniform)
           const unsigned yo = (pix_ok && co < p.cout && !(dbg & 1)) ? (unsigned)((yp * p.y_ld + co) * 2) : OOB;
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), ry, yo, 0, 0);
         }
+      if constexpr (ZW) {
+        // half h keeps bytes 8h .. 8h + 7 of the pixel's 16: even positions from half 0 (sw[0]),
+        // odd ones from half 1 (sw[1]); a store every wave issues, out-of-range lanes dropped
+        const auto sw = __builtin_amdgcn_permlane32_swap(zq[0], zq[1], false, false);
+        const unsigned ev = sw[0], od = sw[1];
+        i32x2 zo;
+        zo[0] = (int)((ev & 0xffu) | ((od & 0xffu) << 8) | ((ev & 0xff00u) << 8) | ((od & 0xff00u) << 16));
+        zo[1] = (int)(((ev >> 16) & 0xffu) | ((od >> 8) & 0xff00u) | ((ev >> 8) & 0xff0000u) | (od & 0xff000000u));
+        const int cz = c0 + wc * 32 * TMC + 64 * hh;  // (cout % 64 == 0: a half's span is whole or absent)
+        const unsigned zo_off = (pix_ok && cz < p.cout) ? (unsigned)(yp * p.zbits_ld + (cz >> 3)) : OOB;
+        __builtin_amdgcn_raw_buffer_store_b64(zo, rzb, zo_off, 0, 0);
+      }
     }
   }
   __builtin_amdgcn_s_waitcnt(0);
@@ -744,10 +822,73 @@ __global__ __launch_bounds__(64 * NWP * NWC) void conv1x1_ring_kernel(const dvie
 
 // operand sets instantiated per tile shape: single K-step, at most 4 accumulators per wave
 // (a single prefetched operand on the 8-accumulator 64->256 tile measured no gain)
-template <int V, int NS, int MT>
+// (bit 8, the bitmap operand: the 128-channel wave tile only)
+// (bit 16, the bitmap writer: one pixel block per wave)
+template <int V, int NS, int MT, int TMC = 4>
 struct PreOk {
-  static constexpr int v = NS != 1 || MT > 4 ? 0 : V;
+  static constexpr int v = NS != 1 || MT > 4 ? 0 : (V & 7) | (TMC == 4 ? (V & 8) : 0) | (MT == TMC && TMC <= 4 ? (V & 16) : 0);
 };
+
+static bool sign_act(int a) { return a == DVIE_ACT_LRELU || a == DVIE_ACT_RELU; }
+static bool ident_out(const dvie_conv_desc& p) {
+  return p.osy == 1 && p.osx == 1 && p.ory == 0 && p.orx == 0 && p.yh == p.oh && p.yw == p.ow;
+}
+// The routing, decided once: conv1x1_launch picks the launcher by tile_1x1, launch_1x1 the
+// ring kernel by ring_takes, and the bitmap predicates below (which the launchers apply and
+// conv1x1_zbits reports) are written in terms of the same two.
+// Tile shapes <channel 32-blocks per wave, stages[, K-step, pixel waves, pixel blocks per wave,
+// channel waves]> (the measurements are in DESIGN.md):
+// * <= 64 output channels, and 65-128 from a single K-step: 64-channel column tiles (two of
+//   them with every epilogue operand prefetched beat one 128-channel tile, 8x128x256 64->128:
+//   33 vs 35 us residual, 48 vs 56 us accumulate + activation input, tools/conv_epi_micro.py)
+// * 65-128 output channels from several K-steps, and wider layers from a single K-step
+//   (layer1's 64->256 forward, the 256-channel data gradients of its 256->64 convs):
+//   128-channel wave tiles of 4 accumulators, every epilogue operand prefetched
+//   (profiles/r03wide1/)
+// * wider layers with several K-steps: the 2-D wave grid of 64-pixel x 128-channel wave tiles
+//   (448->448 heads 724 -> 662 us at 8x256x512)
+enum Tile1x1 { T_2_1, T_2_3, T_4_3, T_4_1, T_WIDE };
+static Tile1x1 tile_1x1(const dvie_conv_desc& p) {
+  const bool one = p.c <= 64;  // a single K-step: one stage, several workgroups per CU
+  if (p.cout <= 64 || (p.cout <= 128 && one)) return one ? T_2_1 : T_2_3;
+  if (p.cout <= 128) return T_4_3;
+  return one ? T_4_1 : T_WIDE;
+}
+// the wide multi-K-step layers without epilogue operands: the five-slot operand ring
+// (256 x 256 tiles, bf16 output)
+static bool ring_takes(const dvie_conv_desc& p) {
+  if (tile_1x1(p) != T_WIDE || p.out_f32) return false;
+  const int npix = p.n * p.oh * p.ow;
+  const int n_tiles = ((p.cout + 255) / 256) * ((npix + 255) / 256);
+  const unsigned long long span = ((unsigned long long)p.n * p.yh * p.yw - 1) * (unsigned long long)p.y_ld * 2ull +
+                                  (unsigned long long)p.cout * 2ull;
+  const unsigned long long xspan = ((unsigned long long)npix - 1) * (unsigned long long)p.x_ld * 2ull + (unsigned long long)p.c * 2ull;
+  return p.c > 64 && n_tiles > 256 && !p.res && !p.beta && !p.dact && span < 0xFFFFFF00ull && xspan < 0xFFFFFF00ull &&
+         p.ih == p.oh && p.iw == p.ow &&
+         (p.act == DVIE_ACT_NONE || (p.act == DVIE_ACT_LRELU && p.alpha >= 0.f && p.alpha <= 1.f));
+}
+// The sign bitmap, bf16 output, identity placement.  Reader (the single-K-step 128-channel
+// wave tile, <4, 1>): one aligned 16-byte load per pixel and wave tile, so whole 128-channel
+// tiles and 16-byte rows.  Writers (a forward: no derivative or accumulation in the same
+// launch): the single-K-step tiles <4, 1> / <2, 1>, where a half wave stores the 8 / 4 bytes of
+// its 64 / 32 channels at once, and the ring kernel (LeakyReLU, 8-byte buffer stores with
+// 32-bit offsets); whole such spans, aligned.
+static bool zb_reads(const dvie_conv_desc& p) {
+  return p.zbits && sign_act(p.dact) && !p.out_f32 && ident_out(p) && tile_1x1(p) == T_4_1 &&
+         ((uintptr_t)p.zbits & 15) == 0 && p.zbits_ld % 16 == 0 && p.cout % 128 == 0;
+}
+static bool zb_writes(const dvie_conv_desc& p) {
+  if (!p.zbits || !sign_act(p.act) || p.dact || p.beta || p.out_f32 || !ident_out(p)) return false;
+  const Tile1x1 t = tile_1x1(p);
+  if (t == T_WIDE) {
+    const unsigned long long zspan = (unsigned long long)p.n * p.yh * p.yw * (unsigned long long)p.zbits_ld;
+    return ring_takes(p) && p.act == DVIE_ACT_LRELU && ((uintptr_t)p.zbits & 7) == 0 && p.zbits_ld % 8 == 0 &&
+           p.cout % 64 == 0 && zspan < 0x7FFFFF00ull;
+  }
+  if (t != T_4_1 && t != T_2_1) return false;
+  const int a = t == T_4_1 ? 8 : 4;
+  return ((uintptr_t)p.zbits & (a - 1)) == 0 && p.zbits_ld % a == 0 && p.cout % (8 * a) == 0;
+}
 
 // DVIE_1X1_DBG (timing only, wrong results; -DDVIE_TIMING_DBG builds only): bit 1 skips the epilogue stores, bit 2 the
 // MFMA loop (operand DMA kept); read per launch
@@ -768,9 +909,13 @@ static bool ce_env_on() {
 }
 
 template <int TMC, int NS, int KC = 64, int NWP = 8, int MI = 1, int NWC = 1>
-static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
+static void launch_1x1(const dvie_conv_desc& p_in, hipStream_t s) {
   typedef G1Cfg<TMC, NS, KC, NWP, MI, NWC> C;
   constexpr int NW = C::NW;
+  // a forward writes the bitmap only under zb_writes (the same answer conv1x1_zbits gives the
+  // caller): any other forward runs without it
+  dvie_conv_desc p = p_in;
+  if (p.zbits && p.act && !zb_writes(p)) p.zbits = nullptr;
   const int npix = p.n * p.oh * p.ow;
   const int n_ct = (p.cout + C::BC - 1) / C::BC;
   const int n_tiles = n_ct * ((npix + C::BP - 1) / C::BP);
@@ -779,13 +924,8 @@ static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
     return;
   }
   if constexpr (NS == 2 && KC == 64 && TMC == 4 && NWP == 4 && MI == 2 && NWC == 2) {
-    // the wide multi-K-step layers without epilogue operands: the five-slot operand ring
-    const unsigned long long span = ((unsigned long long)p.n * p.yh * p.yw - 1) * (unsigned long long)p.y_ld * 2ull +
-                                    (unsigned long long)p.cout * 2ull;
-    const unsigned long long xspan = ((unsigned long long)npix - 1) * (unsigned long long)p.x_ld * 2ull + (unsigned long long)p.c * 2ull;
-    if (p.c > KC && n_tiles > 256 && !p.res && !p.beta && !p.dact && span < 0xFFFFFF00ull &&
-        xspan < 0xFFFFFF00ull && p.ih == p.oh && p.iw == p.ow &&
-        (p.act == DVIE_ACT_NONE || (p.act == DVIE_ACT_LRELU && p.alpha >= 0.f && p.alpha <= 1.f))) {
+    static_assert(C::BC == 256 && C::BP == 256, "ring_takes counts 256 x 256 tiles");
+    if (ring_takes(p)) {
 #ifdef DVIE_TIMING_DBG
       if (p.act == DVIE_ACT_LRELU) switch (dbg_env() & 7) {
 #define DVIE_RING_AB(V)                                                                                                \
@@ -798,7 +938,9 @@ static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
           default: break;
         }
 #endif
-      if (p.act == DVIE_ACT_LRELU)
+      if (p.act == DVIE_ACT_LRELU && p.zbits)
+        DVIE_LAUNCH((conv1x1_ring_kernel<TMC, NWP, MI, NWC, DVIE_ACT_LRELU, 0, true>), dim3(256), dim3(64 * NW), 0, s, p, n_ct, n_tiles);
+      else if (p.act == DVIE_ACT_LRELU)
         DVIE_LAUNCH((conv1x1_ring_kernel<TMC, NWP, MI, NWC, DVIE_ACT_LRELU>), dim3(256), dim3(64 * NW), 0, s, p, n_ct, n_tiles);
       else
         DVIE_LAUNCH((conv1x1_ring_kernel<TMC, NWP, MI, NWC, DVIE_ACT_NONE>), dim3(256), dim3(64 * NW), 0, s, p, n_ct, n_tiles);
@@ -819,11 +961,13 @@ static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
   }
   // single K-step with identity placement: prefetch the epilogue operands (all of them when
   // the registers allow -- MI * TMC <= 4 -- else the activation input, or the residual)
-  const bool ident = p.osy == 1 && p.osx == 1 && p.ory == 0 && p.orx == 0 && p.yh == p.oh && p.yw == p.ow;
+  const bool ident = ident_out(p);
   int pre = 0;
   if constexpr (NS == 1) {
     if (ident && p.c <= KC) {
       pre = MI * TMC > 4 ? 0 : (p.res ? 1 : 0) | (p.beta ? 2 : 0) | (p.dact ? 4 : 0);
+      if ((pre & 4) && zb_reads(p)) pre |= 8;
+      if (p.zbits && p.act) pre |= 16;  // (zb_writes holds: the check above)
     }
   }
   if constexpr (NS == 1 && MI == 1 && 2 * TMC == 8) {
@@ -831,11 +975,12 @@ static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
       switch (pre) {
 #define DVIE_CE_CASE(V)                                                                                              \
   case V:                                                                                                            \
-    DVIE_LAUNCH((conv1x1_kernel<TMC, NS, KC, NWP, MI, NWC, false, PreOk<V, NS, MI * TMC>::v, true>), dim3(n_tiles), \
+    DVIE_LAUNCH((conv1x1_kernel<TMC, NS, KC, NWP, MI, NWC, false, PreOk<V, NS, MI * TMC, TMC>::v, true>), dim3(n_tiles), \
                        dim3(64 * NW), 0, s, p, n_ct, n_tiles, 0);                                                     \
     return;
         DVIE_CE_CASE(0) DVIE_CE_CASE(1) DVIE_CE_CASE(2) DVIE_CE_CASE(3) DVIE_CE_CASE(4)
         DVIE_CE_CASE(5) DVIE_CE_CASE(6) DVIE_CE_CASE(7)
+        DVIE_CE_CASE(12) DVIE_CE_CASE(13) DVIE_CE_CASE(14) DVIE_CE_CASE(15) DVIE_CE_CASE(16) DVIE_CE_CASE(17)
 #undef DVIE_CE_CASE
       }
     }
@@ -843,45 +988,46 @@ static void launch_1x1(const dvie_conv_desc& p, hipStream_t s) {
   switch (pre) {
 #define DVIE_PRE_CASE(V)                                                                                          \
   case V:                                                                                                        \
-    DVIE_LAUNCH((conv1x1_kernel<TMC, NS, KC, NWP, MI, NWC, false, PreOk<V, NS, MI * TMC>::v>), dim3(n_tiles), \
+    DVIE_LAUNCH((conv1x1_kernel<TMC, NS, KC, NWP, MI, NWC, false, PreOk<V, NS, MI * TMC, TMC>::v>), dim3(n_tiles), \
                        dim3(64 * NW), 0, s, p, n_ct, n_tiles, dbg_env());                                                   \
     break;
     DVIE_PRE_CASE(1) DVIE_PRE_CASE(2) DVIE_PRE_CASE(3) DVIE_PRE_CASE(4) DVIE_PRE_CASE(5)
     DVIE_PRE_CASE(6) DVIE_PRE_CASE(7)
+    DVIE_PRE_CASE(12) DVIE_PRE_CASE(13) DVIE_PRE_CASE(14) DVIE_PRE_CASE(15) DVIE_PRE_CASE(16) DVIE_PRE_CASE(17)
 #undef DVIE_PRE_CASE
     default:
       DVIE_LAUNCH((conv1x1_kernel<TMC, NS, KC, NWP, MI, NWC, false>), dim3(n_tiles), dim3(64 * NW), 0, s, p, n_ct, n_tiles, dbg_env());
   }
 }
 
-// Returns true when the 1x1 GEMM kernel took the launch.
-bool conv1x1_launch(const dvie_conv_desc& p, hipStream_t s) {
+static bool takes_1x1(const dvie_conv_desc& p) {
   if (p.dtype != DVIE_BF16 || p.th != 1 || p.tw != 1) return false;
   if (p.sy != 1 || p.sx != 1 || p.dy0 != 0 || p.dx0 != 0 || p.ih != p.oh || p.iw != p.ow) return false;
   if (p.osy < 1 || p.osx < 1 || p.ory < 0 || p.orx < 0) return false;
   if (p.c % 64 != 0 && p.c > 64) return false;
   if ((long long)p.n * p.oh * p.ow >= (1LL << 31)) return false;
-  const int cout = p.cout;
-  const bool one = p.c <= 64;  // a single K-step: one stage, several workgroups per CU
-  // Tile shapes <channel 32-blocks per wave, stages[, K-step, pixel waves, pixel blocks per wave,
-  // channel waves]> (the measurements are in DESIGN.md):
-  // * <= 64 output channels, and 65-128 from a single K-step: 64-channel column tiles (two of
-  //   them with every epilogue operand prefetched beat one 128-channel tile, 8x128x256 64->128:
-  //   33 vs 35 us residual, 48 vs 56 us accumulate + activation input, tools/conv_epi_micro.py)
-  // * 65-128 output channels from several K-steps, and wider layers from a single K-step
-  //   (layer1's 64->256 forward, the 256-channel data gradients of its 256->64 convs):
-  //   128-channel wave tiles of 4 accumulators, every epilogue operand prefetched
-  //   (profiles/r03wide1/)
-  // * wider layers with several K-steps: the 2-D wave grid of 64-pixel x 128-channel wave tiles
-  //   (448->448 heads 724 -> 662 us at 8x256x512)
-  if (cout <= 64 || (cout <= 128 && one))
-    one ? launch_1x1<2, 1>(p, s) : launch_1x1<2, 3>(p, s);
-  else if (cout <= 128)
-    launch_1x1<4, 3>(p, s);
-  else if (one)
-    launch_1x1<4, 1>(p, s);
-  else
-    launch_1x1<4, 2, 64, 4, 2, 2>(p, s);
+  return true;
+}
+
+// 1: this file takes the launch and its kernel honours p.zbits (2: as a writer whose epilogue
+// pays for it -- the ring kernel's runs after its MFMAs, not under an operand DMA), 0: takes it
+// and ignores the bitmap, -1: not a launch of this file.
+int conv1x1_zbits(const dvie_conv_desc& p) {
+  if (!takes_1x1(p)) return -1;
+  if (zb_writes(p)) return tile_1x1(p) == T_WIDE ? 2 : 1;
+  return zb_reads(p);
+}
+
+// Returns true when the 1x1 GEMM kernel took the launch.
+bool conv1x1_launch(const dvie_conv_desc& p, hipStream_t s) {
+  if (!takes_1x1(p)) return false;
+  switch (tile_1x1(p)) {
+    case T_2_1: launch_1x1<2, 1>(p, s); break;
+    case T_2_3: launch_1x1<2, 3>(p, s); break;
+    case T_4_3: launch_1x1<4, 3>(p, s); break;
+    case T_4_1: launch_1x1<4, 1>(p, s); break;
+    case T_WIDE: launch_1x1<4, 2, 64, 4, 2, 2>(p, s); break;
+  }
   return true;
 }
 

@@ -80,6 +80,29 @@ __device__ __forceinline__ void dact_bf16x8(float* w, const i32x4 tz, int dact, 
   dact8(w, z, dact, alpha);
 }
 
+// dact8 for LRELU / RELU with the factor taken from the activation sign bitmap
+// (dvie_conv_desc.zbits): bit k of `bits` is z[k] > 0 of the lane's 8 channels
+__device__ __forceinline__ void dact_bits8(float* w, unsigned bits, int dact, float alpha) {
+  if (dact == DVIE_ACT_LRELU) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] *= (bits >> k) & 1u ? 1.f : alpha;
+  } else if (dact == DVIE_ACT_RELU) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = (bits >> k) & 1u ? w[k] : 0.f;
+  }
+}
+
+// the bitmap byte of 8 packed bf16 results: bit k = (stored value k > 0), what a reader of
+// z computes in dact8 (taken from the rounded bf16, not from the fp32 value before the pack)
+__device__ __forceinline__ unsigned sign_bits8(const i32x4 packed) {
+  float z[8];
+  unpack_bf16x8(packed, z);
+  unsigned bits = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) bits |= (z[k] > 0.f ? 1u : 0u) << k;
+  return bits;
+}
+
 // bf16 epilogue arithmetic from operands already in registers (R residual, B accumulate
 // target, Z activation input; an operand whose flag is off is never read): the packed result,
 // the store is the kernel's
@@ -90,6 +113,17 @@ __device__ __forceinline__ i32x4 epi8_regs(float* w, const dvie_conv_desc& p, co
   if constexpr (B) add_bf16x8(w, *b);
   act8(w, p.act, p.alpha);
   if constexpr (Z) dact_bf16x8(w, *z, p.dact, p.alpha);
+  return pack_bf16x8(w);
+}
+
+// epi8_regs with the activation input as its bitmap byte (LRELU / RELU derivative)
+template <bool R, bool B>
+__device__ __forceinline__ i32x4 epi8_regs_bits(float* w, const dvie_conv_desc& p, const i32x4* r, const i32x4* b,
+                                                unsigned bits) {
+  if constexpr (R) add_bf16x8(w, *r);
+  if constexpr (B) add_bf16x8(w, *b);
+  act8(w, p.act, p.alpha);
+  dact_bits8(w, bits, p.dact, p.alpha);
   return pack_bf16x8(w);
 }
 

@@ -364,10 +364,31 @@ bool conv_halo_launch(const dvie_conv_desc& p, hipStream_t s);  // conv_halo.hip
 bool conv_halo_ph4_launch(const dvie_conv_desc& p, hipStream_t s);  // conv_halo.hip
 bool conv1x1_launch(const dvie_conv_desc& p, hipStream_t s);    // conv1x1.hip
 bool conv_s2_launch(const dvie_conv_desc& p, hipStream_t s);    // conv_s2.hip
+int conv1x1_zbits(const dvie_conv_desc& p);                     // conv1x1.hip
+int conv_halo_zbits(const dvie_conv_desc& p);                   // conv_halo.hip
 
 }  // namespace dvie
 
 using namespace dvie;
+
+// images per launch: the kernels address one launch's input through 32-bit buffer offsets
+static long long batch_chunk(const dvie_conv_desc* d, unsigned long long img_x) {
+  return (long long)(0xFFFFFF00ull / img_x) < d->n ? (long long)(0xFFFFFF00ull / img_x) : d->n;
+}
+
+// Asked in the order dvie_conv2d_fwd offers a launch to the kernel families (each answers -1
+// when the launch is not its own): the answer of the family that takes it.  A launch that
+// runs as several batch chunks, a phase-split one and the kernels after the halo family: 0.
+extern "C" int dvie_conv_zbits(const dvie_conv_desc* d) {
+  if (!d || !d->zbits || d->dtype != DVIE_BF16 || d->out_f32 || d->phc) return 0;
+  if (d->zbits_ld <= 0 || d->ih <= 0 || d->iw <= 0) return 0;
+  if (d->x_ld <= 0 || d->n <= 0) return 0;
+  const unsigned long long img_x = (unsigned long long)d->ih * d->iw * d->x_ld * 2ull;
+  if (img_x >= 0xFFFFFF00ull || batch_chunk(d, img_x) < d->n) return 0;
+  int r = conv1x1_zbits(*d);
+  if (r < 0) r = conv_halo_zbits(*d);
+  return r > 0 ? r : 0;
+}
 
 extern "C" int dvie_conv2d_fwd(const dvie_conv_desc* d, void* stream) {
   DVIE_CHECK_ARG(d && d->x && d->w && d->y, "conv: null pointer");
@@ -395,7 +416,7 @@ extern "C" int dvie_conv2d_fwd(const dvie_conv_desc* d, void* stream) {
   DVIE_CHECK_ARG(wb < 0xFFFFFF00ull, "conv: weights exceed the 4 GiB buffer range");
   DVIE_CHECK_ARG(img_x < 0xFFFFFF00ull, "conv: one input image exceeds the 4 GiB buffer range");
   hipStream_t s = (hipStream_t)stream;
-  const long long chunk = (long long)(0xFFFFFF00ull / img_x) < d->n ? (long long)(0xFFFFFF00ull / img_x) : d->n;
+  const long long chunk = batch_chunk(d, img_x);
   const int oes = (d->out_f32 || d->dtype == DVIE_F32) ? 4 : 2;
   const unsigned long long img_y = (unsigned long long)d->yh * d->yw;
   for (long long n0 = 0; n0 < d->n; n0 += chunk) {
@@ -405,6 +426,7 @@ extern "C" int dvie_conv2d_fwd(const dvie_conv_desc* d, void* stream) {
     c.y = (char*)d->y + n0 * img_y * d->y_ld * oes;
     if (d->res) c.res = (const char*)d->res + n0 * img_y * d->res_ld * oes;
     if (d->z) c.z = (const char*)d->z + n0 * img_y * d->z_ld * es;
+    if (d->zbits) c.zbits = (char*)d->zbits + n0 * img_y * d->zbits_ld;
     if (c.phc) {  // the one-launch stride-2 data gradient: the halo kernel only
       DVIE_CHECK_ARG(conv_halo_ph4_launch(c, s), "conv: phase-split output (phc=%d) needs bf16, 2x2 taps at "
                      "(0,0), osy=osx=2, cout=4*phc, phc %% 32 == 0, no bias", c.phc);

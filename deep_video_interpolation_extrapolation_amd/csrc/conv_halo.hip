@@ -983,7 +983,10 @@ struct NkCfg {
   static constexpr int NS = (NG + 1) / 2;    // 16-deep MFMA slices
 };
 
-template <int CP8, bool OUTF32, bool PRE = false>
+// ZB (with PRE, a ReLU / LeakyReLU derivative): the activation input comes from the sign
+// bitmap (dvie_conv_desc.zbits), one dword (the wave's 32 channels of a pixel) per accumulator
+// in place of two 16-byte z loads
+template <int CP8, bool OUTF32, bool PRE = false, bool ZB = false>
 __global__ __launch_bounds__(512, 2) void conv_nk_kernel(const dvie_conv_desc p, int n_cb, int n_tiles, int tiles_x,
                                                         int tiles_y) {
   typedef NkCfg<CP8> C;
@@ -1078,11 +1081,14 @@ __global__ __launch_bounds__(512, 2) void conv_nk_kernel(const dvie_conv_desc p,
         (void*)p.res, 0,
         p.res ? (int)(((unsigned long long)p.n * p.yh * p.yw - 1) * (unsigned long long)p.res_ld * 2ull + p.cout * 2ull) : 0,
         0x00020000);
+    static_assert(!ZB || PRE, "bitmap operand: the prefetch form");
     const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.z, 0,
-        p.dact ? (int)(((unsigned long long)p.n * p.yh * p.yw - 1) * (unsigned long long)p.z_ld * 2ull + p.cout * 2ull) : 0,
+        ZB ? (void*)p.zbits : (void*)p.z, 0,
+        ZB ? (int)(((unsigned long long)p.n * p.yh * p.yw - 1) * (unsigned long long)p.zbits_ld + p.cout / 8)
+           : p.dact ? (int)(((unsigned long long)p.n * p.yh * p.yw - 1) * (unsigned long long)p.z_ld * 2ull + p.cout * 2ull) : 0,
         0x00020000);
-    const int nops = (p.res ? 1 : 0) + (p.beta ? 1 : 0) + (p.dact ? 1 : 0);
+    // operand loads per prefetch (the counted wait below): 4 per 16-byte operand, 2 bitmap dwords
+    const int nloads = 4 * ((p.res ? 1 : 0) + (p.beta ? 1 : 0)) + (ZB ? 2 : p.dact ? 4 : 0);
     // the lane's element offsets of accumulator b, pair P in the three operand images (or OOB)
     auto offs = [&](const TP& T, int b, int P, unsigned& oy_, unsigned& or_, unsigned& oz_) {
       const int oy = T.y0 + wp, ox = T.x0 + 32 * b + r32, co = co0 + 16 * P;
@@ -1090,10 +1096,11 @@ __global__ __launch_bounds__(512, 2) void conv_nk_kernel(const dvie_conv_desc p,
       const long long pix = ((long long)T.n * p.yh + oy * p.osy + p.ory) * p.yw + ox * p.osx + p.orx;
       oy_ = ok ? (unsigned)((pix * p.y_ld + co) * 2) : OOB;
       or_ = ok ? (unsigned)((pix * p.res_ld + co) * 2) : OOB;
-      oz_ = ok ? (unsigned)((pix * p.z_ld + co) * 2) : OOB;
+      oz_ = !ok ? OOB : ZB ? (unsigned)(pix * p.zbits_ld + ((co0 - 8 * hh) >> 3)) : (unsigned)((pix * p.z_ld + co) * 2);
     };
     // one i32x4 per (operand, b, P); a flag-off operand is never read (its loads are not issued)
     i32x4 er[2][2], eb[2][2], ez[2][2];
+    unsigned ezb[2] = {0u, 0u};  // (ZB) byte 2 P + hh of accumulator b's dword is the lane's
     auto prefetch = [&](const TP& T) {
 #pragma unroll
       for (int b = 0; b < 2; ++b)
@@ -1103,7 +1110,11 @@ __global__ __launch_bounds__(512, 2) void conv_nk_kernel(const dvie_conv_desc p,
           offs(T, b, P, o_y, o_r, o_z);
           if (p.res) er[b][P] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, o_r, 0, 0));
           if (p.beta) eb[b][P] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, o_y, 0, 0));
-          if (p.dact) ez[b][P] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, o_z, 0, 0));
+          if constexpr (ZB) {
+            if (P == 0) ezb[b] = __builtin_amdgcn_raw_buffer_load_b32(rz, o_z, 0, 0);
+          } else {
+            if (p.dact) ez[b][P] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, o_z, 0, 0));
+          }
         }
     };
     f32x4 bia[2][2];
@@ -1156,7 +1167,10 @@ __global__ __launch_bounds__(512, 2) void conv_nk_kernel(const dvie_conv_desc p,
           if (p.res) add_bf16x8(w, er[b][P]);
           if (p.beta) add_bf16x8(w, eb[b][P]);
           act8(w, p.act, p.alpha);
-          if (p.dact) dact_bf16x8(w, ez[b][P], p.dact, p.alpha);
+          if constexpr (ZB)
+            dact_bits8(w, (ezb[b] >> (8 * (2 * P + hh))) & 0xffu, p.dact, p.alpha);
+          else if (p.dact)
+            dact_bf16x8(w, ez[b][P], p.dact, p.alpha);
           const i32x4 o = pack_bf16x8(w);
           unsigned o_y, o_r, o_z;
           offs(cur, b, P, o_y, o_r, o_z);
@@ -1164,8 +1178,8 @@ __global__ __launch_bounds__(512, 2) void conv_nk_kernel(const dvie_conv_desc p,
         }
       }
       prefetch(nxt);
-      // outstanding, oldest first: [next halo][4 stores][4 nops operand loads]
-      wait_vmcnt(4 + 4 * nops);
+      // outstanding, oldest first: [next halo][4 stores][nloads operand loads]
+      wait_vmcnt(4 + nloads);
       __builtin_amdgcn_s_barrier();
       cur = nxt;
     }
@@ -1211,6 +1225,16 @@ static bool nk_pre_on() {
   return !(e && *e == '0');
 }
 
+// the dense-K kernel takes the derivative from the sign bitmap: the prefetch form (bf16
+// output, 32-bit spans), dword loads of a wave's 32 channels
+static bool nk_zb_reads(const dvie_conv_desc& p) {
+  if (!p.zbits || !(p.dact == DVIE_ACT_LRELU || p.dact == DVIE_ACT_RELU) || p.out_f32 || !nk_pre_on()) return false;
+  if (((uintptr_t)p.zbits & 3) != 0 || p.zbits_ld % 4 != 0 || p.cout % 32 != 0) return false;
+  const unsigned long long opix = (unsigned long long)p.n * p.yh * p.yw - 1;
+  return (opix * p.y_ld + p.cout) * 2ull < 0xFFFFFF00ull && (!p.res || (opix * p.res_ld + p.cout) * 2ull < 0xFFFFFF00ull) &&
+         opix * (unsigned long long)p.zbits_ld + p.cout / 8 < 0x7FFFFF00ull;
+}
+
 template <int CP8>
 static void launch_nk(const dvie_conv_desc& p, hipStream_t s) {
   typedef NkCfg<CP8> C;
@@ -1228,6 +1252,8 @@ static void launch_nk(const dvie_conv_desc& p, hipStream_t s) {
                         (!p.dact || (opix * p.z_ld + p.cout) * 2ull < 0xFFFFFF00ull);
   if (p.out_f32)
     DVIE_LAUNCH((conv_nk_kernel<CP8, true>), dim3(grid), dim3(512), 0, s, p, n_cb, n_tiles, tiles_x, tiles_y);
+  else if (nk_zb_reads(p))
+    DVIE_LAUNCH((conv_nk_kernel<CP8, false, true, true>), dim3(grid), dim3(512), 0, s, p, n_cb, n_tiles, tiles_x, tiles_y);
   else if (nk_pre_on() && spans_ok && (p.res || p.beta || p.dact))  // (no operands: the seg encoder's
     // 20 -> 32 forward measured 0.136 -> 0.142 ms with the prefetch form, profiles/r06/nkpre_*)
     DVIE_LAUNCH((conv_nk_kernel<CP8, false, true>), dim3(grid), dim3(512), 0, s, p, n_cb, n_tiles, tiles_x, tiles_y);
@@ -1488,9 +1514,14 @@ __global__ __launch_bounds__(512) void conv_h8_kernel(const dvie_conv_desc p, in
           (void*)((const bf16_t*)p.res + ((EPI & 1) ? pix0 * p.res_ld : 0)), 0, 0x7FFFFFF0, 0x00020000);
       const __amdgpu_buffer_rsrc_t rb =
           __builtin_amdgcn_make_buffer_rsrc((void*)((const bf16_t*)p.y + pix0 * p.y_ld), 0, 0x7FFFFFF0, 0x00020000);
+      // (EPI & 8: the activation input from the sign bitmap, one dword = 32 channels per group)
+      constexpr bool ZB = (EPI & 8) != 0;
+      static_assert(!ZB || (EPI & 4) != 0, "bitmap operand: with the activation derivative");
       const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)((const bf16_t*)p.z + ((EPI & 4) ? pix0 * p.z_ld : 0)), 0, 0x7FFFFFF0, 0x00020000);
+          ZB ? (void*)((const char*)p.zbits + pix0 * p.zbits_ld)
+             : (void*)((const bf16_t*)p.z + ((EPI & 4) ? pix0 * p.z_ld : 0)), 0, 0x7FFFFFF0, 0x00020000);
       i32x4 o_r[2][2], o_b[2][2], o_z[2][2];  // [buffer][P]
+      unsigned o_zb[2] = {0u, 0u};            // [buffer]
       // group gi: row r = gi >> 2, pixel half b = (gi >> 1) & 1, channel block i = gi & 1
       auto epi_load = [&](int gi) {
         const int i = gi & 1, r = gi >> 2, b = (gi >> 1) & 1, u = gi & 1;
@@ -1502,7 +1533,9 @@ __global__ __launch_bounds__(512) void conv_h8_kernel(const dvie_conv_desc p, in
             const long long dp = (long long)(2 * wp + r) * p.osy * p.yw + (long long)(32 * b + r32) * p.osx;
             if (EPI & 1) o_r[u][P] = __builtin_amdgcn_raw_buffer_load_b128(rr, ok ? (unsigned)((dp * p.res_ld + co) * 2) : OOB, 0, 0);
             if (EPI & 2) o_b[u][P] = __builtin_amdgcn_raw_buffer_load_b128(rb, ok ? (unsigned)((dp * p.y_ld + co) * 2) : OOB, 0, 0);
-            if (EPI & 4) o_z[u][P] = __builtin_amdgcn_raw_buffer_load_b128(rz, ok ? (unsigned)((dp * p.z_ld + co) * 2) : OOB, 0, 0);
+            if ((EPI & 4) && !ZB) o_z[u][P] = __builtin_amdgcn_raw_buffer_load_b128(rz, ok ? (unsigned)((dp * p.z_ld + co) * 2) : OOB, 0, 0);
+            if (ZB && P == 0)  // the dword of channels co - 8 hh .. + 31: byte 2 P + hh is this lane's
+              o_zb[u] = __builtin_amdgcn_raw_buffer_load_b32(rz, ok ? (unsigned)(dp * p.zbits_ld + ((J.c0 + wc * 64 + 32 * i) >> 3)) : OOB, 0, 0);
           }
       };
       if (EPI) epi_load(0);
@@ -1530,7 +1563,9 @@ __global__ __launch_bounds__(512) void conv_h8_kernel(const dvie_conv_desc p, in
             const int co = J.c0 + wc * 64 + 32 * i + 16 * P + 8 * hh;
             float* w = v8[P];
             if (p.bias) add_f32x8(w, p.bias + co);
-            const i32x4 o = epi8_regs<(EPI & 1) != 0, (EPI & 2) != 0, (EPI & 4) != 0>(w, p, &o_r[u][P], &o_b[u][P], &o_z[u][P]);
+            const i32x4 o = ZB ? epi8_regs_bits<(EPI & 1) != 0, (EPI & 2) != 0>(w, p, &o_r[u][P], &o_b[u][P],
+                                                                                (o_zb[u] >> (8 * (2 * P + hh))) & 0xffu)
+                               : epi8_regs<(EPI & 1) != 0, (EPI & 2) != 0, (EPI & 4) != 0>(w, p, &o_r[u][P], &o_b[u][P], &o_z[u][P]);
             if (ok) __builtin_amdgcn_raw_buffer_store_b128(o, rb, (unsigned)((dp * p.y_ld + co) * 2), 0, 0);
           }
         }
@@ -1555,17 +1590,30 @@ static void launch_h8(const dvie_conv_desc& p, hipStream_t s, int n_ct, int n_ti
   DVIE_LAUNCH((conv_h8_kernel<EPI>), dim3(grid), dim3(H8::NTH), 0, s, p, n_ct, n_tiles, tiles_x, tiles_y);
 }
 
+static bool h8_takes(const dvie_conv_desc& p) {
+  if (!h8_on() || p.out_f32 || p.c % 32 != 0 || p.c < 64 || p.cout % 128 != 0) return false;
+  const long long nt = (long long)(p.cout / H8::BC) * ((p.ow + 63) / 64) * ((p.oh + H8::PR - 1) / H8::PR) * p.n;
+  return nt >= 224 && nt < (1LL << 30);  // fewer tiles than CUs: the 4-row kernel
+}
+
+// the eight-row kernel takes the activation derivative (LRELU / RELU) from the sign bitmap:
+// dword loads of 32 channels, offsets within the 2 GB buffer range
+static bool h8_zb_reads(const dvie_conv_desc& p) {
+  if (!p.zbits || !(p.dact == DVIE_ACT_LRELU || p.dact == DVIE_ACT_RELU)) return false;
+  if (((uintptr_t)p.zbits & 3) != 0 || p.zbits_ld % 4 != 0) return false;
+  return (unsigned long long)p.n * p.yh * p.yw * (unsigned long long)p.zbits_ld < 0x7FFFFF00ull;
+}
+
 // 3x3 stride-1 conv, identity taps (t3), bf16 output; true when the eight-row kernel took it
 static bool conv_h8_launch(const dvie_conv_desc& p, hipStream_t s) {
-  if (!h8_on() || p.out_f32 || p.c % 32 != 0 || p.c < 64 || p.cout % 128 != 0) return false;
+  if (!h8_takes(p)) return false;
   const int n_ct = p.cout / H8::BC, tiles_x = (p.ow + 63) / 64, tiles_y = (p.oh + H8::PR - 1) / H8::PR;
-  const long long nt = (long long)n_ct * tiles_x * tiles_y * p.n;
-  if (nt < 224 || nt >= (1LL << 30)) return false;  // fewer tiles than CUs: the 4-row kernel
-  const int n_tiles = (int)nt;
-  switch ((p.res ? 1 : 0) | (p.beta ? 2 : 0) | (p.dact ? 4 : 0)) {
+  const int n_tiles = n_ct * tiles_x * tiles_y * p.n;
+  switch ((p.res ? 1 : 0) | (p.beta ? 2 : 0) | (p.dact ? 4 : 0) | (h8_zb_reads(p) ? 8 : 0)) {
 #define DVIE_H8(EPI) \
   case EPI: launch_h8<EPI>(p, s, n_ct, n_tiles, tiles_x, tiles_y); break;
     DVIE_H8(0) DVIE_H8(1) DVIE_H8(2) DVIE_H8(3) DVIE_H8(4) DVIE_H8(5) DVIE_H8(6) DVIE_H8(7)
+    DVIE_H8(12) DVIE_H8(13) DVIE_H8(14) DVIE_H8(15)
 #undef DVIE_H8
   }
   return true;
@@ -1588,8 +1636,7 @@ bool conv_halo_ph4_launch(const dvie_conv_desc& p, hipStream_t s) {
   return p.cout % 128 != 0 ? try_halo<1, 2, 4, 2, 2, true>(p, s) : try_halo<2, 2, 4, 2, 2, true>(p, s);
 }
 
-// Returns true when the halo kernel took the launch.
-bool conv_halo_launch(const dvie_conv_desc& p, hipStream_t s) {
+static bool halo_takes(const dvie_conv_desc& p) {
   if (p.dtype != DVIE_BF16) return false;
   if (p.sy != 1 || p.sx != 1 || p.ddy != 1 || p.ddx != 1) return false;
   if (p.osy < 1 || p.osx < 1 || p.ory < 0 || p.orx < 0) return false;
@@ -1602,7 +1649,30 @@ bool conv_halo_launch(const dvie_conv_desc& p, hipStream_t s) {
   // 32-bit halo offsets: the input's byte span must fit (dvie_conv2d_fwd rejects larger
   // inputs for every kernel; kept here so the halo path never relies on the caller)
   if (((pix - 1) * (unsigned long long)p.x_ld + (unsigned long long)p.c) * 2ull >= 0xFFFFFF00ull) return false;
-  if (t3 && p.c % 8 == 0 && p.c <= 24 && p.kpad >= 9 * p.c) {
+  return true;
+}
+
+// 1: a kernel of this file takes the launch and honours p.zbits, 0: takes it and ignores the
+// bitmap, -1: not a launch of this file.  Only the eight-row kernel reads the bitmap; the
+// kernels asked before it in conv_halo_launch (narrow input, strip, narrow output) all need
+// cout <= 64, which h8_takes excludes.
+static bool nk_takes(const dvie_conv_desc& p) {  // (after halo_takes, 3x3 taps)
+  return p.c % 8 == 0 && p.c <= 24 && p.kpad >= 9 * p.c;
+}
+
+int conv_halo_zbits(const dvie_conv_desc& p) {
+  if (!halo_takes(p)) return -1;
+  if (p.th != 3 || p.tw != 3) return 0;
+  if (nk_takes(p)) return nk_zb_reads(p);
+  return h8_takes(p) && h8_zb_reads(p);
+}
+
+// Returns true when the halo kernel took the launch.
+bool conv_halo_launch(const dvie_conv_desc& p, hipStream_t s) {
+  if (!halo_takes(p)) return false;
+  const bool t1 = p.th == 1 && p.tw == 1, t3 = p.th == 3 && p.tw == 3;
+  const bool t22 = p.th == 2 && p.tw == 2, t12 = p.th == 1 && p.tw == 2, t21 = p.th == 2 && p.tw == 1;
+  if (t3 && nk_takes(p)) {
     switch (p.c / 8) {
       case 1: launch_nk<1>(p, s); break;
       case 2: launch_nk<2>(p, s); break;

@@ -763,6 +763,15 @@ class Plan:
         self._i2c = None  # im2col scratch shared by the layers that take that lowering
         self.ws = None  # workspace of the weight-gradient / column-sum partials
         self.ws_floats = 1
+        # activation sign bitmaps (include/dvie.h dvie_conv_desc.zbits): buffer name -> its
+        # bitmap, a uint8 tensor of its own (never part of an activation / gradient storage)
+        self.zbits = {}
+        # DVIE_ZBITS, read here, at plan compile time: 0 none, 1 (default) the writers that cost
+        # their launch nothing (dvie_conv_zbits == 1), 2 also the ring 1x1 writer (heads.0)
+        self._zbits_level = int(os.environ.get("DVIE_ZBITS", "1") or 0)
+        self._zbits_on = self._zbits_level > 0
+        self._fwd_conv = {}  # id(ConvOp) -> its forward op
+        self._zb = {}  # id(buffer) -> bitmap candidate (_zbits_region / _zbits_settle)
         self._alloc()
         self._build_pack()
         self._build_forward()
@@ -1077,6 +1086,8 @@ class Plan:
                                              + lay.cout * lay.cin * lay.kh * lay.kw)))
         if ext:
             self.ext_out.setdefault(out.buf.name, []).append((len(self.fwd), out))
+        else:
+            self._fwd_conv[id(op)] = o
         self.fwd.append(o)
 
     def _convT_fwd(self, op):
@@ -1329,9 +1340,73 @@ class Plan:
             epi = Epilogue(beta=0 if i == 0 else 1, res=r[0] if r else None, res_ld=r[1] if r else 0)
             if i == len(seq) - 1:
                 epi = epi._replace(dact=dact, z=z, z_ld=b.C)
-            self.bwd.extend(em(epi))
+            n_placed = len(self.bwd)
+            ops = em(epi)
+            if fuse_dact and i == len(seq) - 1:
+                self._zbits_region(b, region, prod[0], ops, self.bwd[n_placed:])
+            self.bwd.extend(ops)
         b.n_flushed += 1
         b.done = b.n_flushed == len(b.expected)
+
+    # ---- activation sign bitmaps: a buffer gets one when the derivative of its (ReLU /
+    # LeakyReLU) producer rides on data-gradient kernels that read the bitmap
+    # (dvie_conv_zbits: asked of the library, where the kernels are chosen) in every region,
+    # and the producer's forward kernel writes it.  z stays in every descriptor. ----
+    def _zbits_region(self, b, region, prod, ops, placed):
+        """The derivative of `prod` rides on `ops` for `region` of b (`placed`: the ops the
+        emitter appended itself): point the carriers at b's bitmap (provisionally,
+        _zbits_settle decides) or mark b as not covered."""
+        if not self._zbits_on or self.dtype != torch.bfloat16 or prod.act not in (L.ACT_LRELU, L.ACT_RELU):
+            return
+        st = self._zb.setdefault(id(b), dict(buf=b, prod=prod, users=[], regions=set(), ok=True, t=None))
+        fo = self._fwd_conv.get(id(prod))
+        if not ops and any(o.kind == L.OP_HEAD3_BWD and o.u.head3.dact for o in placed):
+            # the fused head backward stages the hidden map once for its weight gradient and
+            # takes act' from that tile in LDS: no second stream of z, nothing for a bitmap to save
+            st["regions"].add(region.key())
+            return
+        dact_of = {L.OP_CONV: lambda o: o.u.conv.dact, L.OP_EW: lambda o: o.u.ew.dact, L.OP_ATTN: lambda o: o.u.attn.dact}
+        carriers = [o for o in ops if dact_of.get(o.kind, lambda o: 1)(o)]
+        if (fo is None or b.C % 8 or region.c0 % 8 or prod.out.c0 % 8 or not carriers
+                or any(o.kind != L.OP_CONV for o in carriers)):
+            st["ok"] = False
+            return
+        if st["t"] is None:
+            st["t"] = torch.empty(self.nf * b.H * b.W * b.C // 8, dtype=torch.uint8, device=self.device)
+        for o in carriers:
+            d = o.u.conv
+            d.zbits, d.zbits_ld = st["t"].data_ptr() + region.c0 // 8, b.C // 8
+            st["users"].append((o, region))
+            st["regions"].add(region.key())
+            if not L.load().dvie_conv_zbits(ctypes.byref(d)):
+                st["ok"] = False
+
+    def _zbits_settle(self):
+        """After the backward list is complete: keep the bitmaps whose every reader and whose
+        writer are covered (the writer's descriptor gets zbits now), drop the others."""
+        for st in self._zb.values():
+            b, prod = st["buf"], st["prod"]
+            ok = st["ok"] and st["t"] is not None and len(st["regions"]) == len(b.expected)
+            if ok:
+                d = self._fwd_conv[id(prod)].u.conv
+                d.zbits, d.zbits_ld = st["t"].data_ptr() + prod.out.c0 // 8, b.C // 8
+                ok = 0 < L.load().dvie_conv_zbits(ctypes.byref(d)) <= self._zbits_level
+                if not ok:
+                    d.zbits, d.zbits_ld = None, 0
+            if not ok:
+                for o, _ in st["users"]:
+                    o.u.conv.zbits, o.u.conv.zbits_ld = None, 0
+                continue
+            self.zbits[b.name] = st["t"]
+            self.keep.append(st["t"])
+            # profiling meta: a reader streams 1 bit per element in place of 2 bytes, the
+            # writer adds the bitmap to its output
+            for o, r in st["users"]:
+                d = o.u.conv
+                o.meta["bytes"] -= float(d.n * d.oh * d.ow * d.cout) * (self.es - 0.125)
+            fo = self._fwd_conv[id(prod)]
+            fo.meta["bytes"] += float(self.nf * b.H * b.W * prod.out.c) / 8
+        self._zb = {}
 
     def _ensure_dact(self, op):
         """Producer-side activation derivative when it could not be fused upstream."""
@@ -1438,6 +1513,7 @@ class Plan:
             if bf.needs_grad and bf.expected and not bf.done:
                 raise RuntimeError(f"incomplete gradient for {bf}: pending {({k: len(v) for k, v in bf.pending.items()})}"
                                    f" of {bf.expected}")
+        self._zbits_settle()
 
     def _out_nchw_backward(self, op, gout, gld):
         pass  # (an output's gradient is seeded in _build_backward; an export has none)

@@ -91,9 +91,25 @@ typedef struct dvie_conv_desc {
                   (b = 0) has no i = 1 (j = 1) taps: those MFMAs are skipped, not multiplied by
                   zero.  bf16, phc % 32 == 0, no bias / fp32 output. */
   int pad1;
+  /* Activation sign bitmap (bf16, act / dact DVIE_ACT_RELU or DVIE_ACT_LRELU; NULL: absent).
+     Byte pix * zbits_ld + c / 8, bit c % 8, is set iff the stored bf16 z[pix][c] > 0 (so -0.0,
+     +0.0 and NaN give 0); zbits_ld = the buffer's channel count / 8, and a region at channel
+     offset c0 (a multiple of 8) passes zbits advanced by c0 / 8.  With act set, a forward kernel
+     that knows the bitmap writes it next to y (from the packed bf16 result); with dact set, a
+     data-gradient kernel that knows it takes act'(z) from it instead of reading z.  z / z_ld
+     stay valid: a kernel that does not know the bitmap reads z (and writes no bitmap), which
+     dvie_conv_zbits tells the caller beforehand. */
+  void* zbits;
+  long long zbits_ld;
 } dvie_conv_desc;
 
 int dvie_conv2d_fwd(const dvie_conv_desc* d, void* stream);
+
+/* Nonzero when the kernel dvie_conv2d_fwd chooses for *d honours d->zbits: writes the bitmap
+ * (d->act set) or reads it in place of z (d->dact set); 0 when that kernel ignores it.
+ * 1: at (nearly) no cost to the launch; 2: a writer that pays for it in its epilogue (the
+ * multi-K-step ring 1x1 kernel: +8% on heads.0), for the caller to weigh against its readers. */
+int dvie_conv_zbits(const dvie_conv_desc* d);
 
 /*
  * Weight gradient of the convolution above (replaces nn.Conv2d backward-weight):
