@@ -287,7 +287,7 @@ EXPORTS = [
     "dvie_adam_dev", "dvie_mfma_probe", "dvie_launch_probe", "dvie_sum_f32", "dvie_wgrad_bias_slabs", "dvie_head3_bwd",
     "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_pack_blocks", "dvie_trace_kernels", "dvie_traced_kernels",
     "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_score_ws_bytes",
-    "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits",
+    "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits", "dvie_bn_partial_doubles",
 ]
 
 _lib = None
@@ -344,6 +344,8 @@ def load():
         lib.dvie_warp_ws_floats.restype = ctypes.c_size_t
         lib.dvie_loss_ws_floats.argtypes = [vp]
         lib.dvie_loss_ws_floats.restype = ctypes.c_size_t
+        lib.dvie_bn_partial_doubles.argtypes = [vp]
+        lib.dvie_bn_partial_doubles.restype = ctypes.c_size_t
         lib.dvie_synth_score_ws_bytes.argtypes = [vp]
         lib.dvie_synth_score_ws_bytes.restype = ctypes.c_size_t
         lib.dvie_adamax.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]

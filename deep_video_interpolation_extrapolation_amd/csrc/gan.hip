@@ -361,6 +361,15 @@ int dvie_bn_partial_splits(const dvie_bn_desc* d) {
   return (int)s;
 }
 
+// forward: splits rows of [2][c] partial sums; backward: the same, then bn_fold_bwd_kernel
+// writes its four coefficient rows over partial[0 .. 4c) whatever splits is
+size_t dvie_bn_partial_doubles(const dvie_bn_desc* d) {
+  if (!d || d->c <= 0) return 0;
+  const size_t sums = (size_t)dvie_bn_partial_splits(d) * 2 * (size_t)d->c;
+  const size_t coef = 4 * (size_t)d->c;
+  return sums > coef ? sums : coef;
+}
+
 int dvie_bn_fwd(const dvie_bn_desc* d, void* stream) {
   int rc = bn_check(d);
   if (rc) return rc;

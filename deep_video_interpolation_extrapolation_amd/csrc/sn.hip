@@ -134,7 +134,8 @@ static int sn_launch(const dvie_sn_layer* layers, int n, const float* state, hip
   for (int i = 0; i < n; ++i) {
     const dvie_sn_layer& l = layers[i];
     DVIE_CHECK_ARG(l.w_bar && l.h > 0 && l.width > 0 && l.state_off >= 0, "sn layer %d: shape", i);
-    DVIE_CHECK_ARG((l.h + 2LL * l.width) * 4 <= 65536, "sn layer %d: h %d width %d exceed the LDS vectors", i, l.h,
+    // v (width), u (h), W v (h): what the launch below allocates
+    DVIE_CHECK_ARG((l.width + 2LL * l.h) * 4 <= 65536, "sn layer %d: h %d width %d exceed the LDS vectors", i, l.h,
                    l.width);
     if (!bwd)
       DVIE_CHECK_ARG(l.u && l.v && l.w_eff && l.power_iterations >= 0, "sn fwd layer %d: pointers", i);

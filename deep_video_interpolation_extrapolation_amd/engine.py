@@ -850,17 +850,20 @@ class Plan:
                     assert a0 + ac <= b0, f"{b}: consumers read overlapping regions {keys}"
         self.l1_out = torch.zeros(max(1, g.n_l1), dtype=torch.float32, device=self.device)
         self.keep.append(self.l1_out)
+        # one partial workspace for every BatchNorm (they run one after another on one stream):
+        # the largest dvie_bn_partial_doubles over the ops, forward (nf) and backward (nb) rows
+        doubles = 8
         for op in g.ops:
             if isinstance(op, BNOp):
                 d = L.BnDesc()
-                d.rows = self.nf * op.x.H * op.x.W
-                self.bn_splits = max(self.bn_splits, L.load().dvie_bn_partial_splits(ctypes.byref(d)))
-                d.rows = self.nb * op.x.H * op.x.W
-                self.bn_splits = max(self.bn_splits, L.load().dvie_bn_partial_splits(ctypes.byref(d)))
+                d.c = op.x.c
+                for n in (self.nf, self.nb):
+                    d.rows = n * op.x.H * op.x.W
+                    self.bn_splits = max(self.bn_splits, L.load().dvie_bn_partial_splits(ctypes.byref(d)))
+                    doubles = max(doubles, L.load().dvie_bn_partial_doubles(ctypes.byref(d)))
                 op.stats = torch.zeros((8, op.x.c), dtype=torch.float32, device=self.device)
                 self.keep.append(op.stats)
-        maxc = max([op.x.c for op in g.ops if isinstance(op, BNOp)] + [4])
-        self.bn_partial = torch.zeros(self.bn_splits * 2 * maxc, dtype=torch.float64, device=self.device)
+        self.bn_partial = torch.zeros(doubles, dtype=torch.float64, device=self.device)
         self.keep.append(self.bn_partial)
 
     def ptr(self, region, n0=0, grad=False):

@@ -449,8 +449,11 @@ int dvie_launch_probe(int blocks, int threads, void* stream);
  *   backward: g = dL/d(pre-activation output) (the engine applies act' upstream);
  *             dgamma (+)= sum g*xhat, dbeta (+)= sum g (accumulate selects +=);
  *             dx (+)= gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)) (beta_dx selects +=).
- * partial: double [splits][2][c] workspace (splits = dvie_bn_partial_splits); stats: fp32
- * [8][c] per-call state written by the forward and read by the backward.
+ * partial: workspace of dvie_bn_partial_doubles(d) doubles = max(splits * 2 * c, 4 * c): the
+ * forward and the backward statistics use it as [splits][2][c] (splits =
+ * dvie_bn_partial_splits), and the backward then reuses its first 4 * c doubles as four
+ * coefficient rows [4][c], which is the larger need when splits is 1.  stats: fp32 [8][c]
+ * per-call state written by the forward and read by the backward.
  * Constraints: c % 4 == 0, c <= 1024, lds % 4 == 0.
  */
 typedef struct dvie_bn_desc {
@@ -476,6 +479,7 @@ typedef struct dvie_bn_desc {
 int dvie_bn_fwd(const dvie_bn_desc* d, void* stream);
 int dvie_bn_bwd(const dvie_bn_desc* d, void* stream);
 int dvie_bn_partial_splits(const dvie_bn_desc* d);
+size_t dvie_bn_partial_doubles(const dvie_bn_desc* d); /* reads rows and c */
 
 /*
  * Discriminator head: AvgPool2d(pool) of an NHWC (n, h, w, c) map, then
