@@ -23,6 +23,8 @@ OP_CONV, OP_WGRAD, OP_WREDUCE, OP_COLSUM, OP_EW, OP_LOSS, OP_PACK = 1, 2, 3, 4, 
 OP_BN_FWD, OP_BN_BWD, OP_HEAD_FWD, OP_HEAD_BWD, OP_ATTN, OP_HEAD3_BWD, OP_SEGENC_FWD = 8, 9, 10, 11, 12, 13, 14
 OP_SEGENC_BWD = 15
 OP_WREDUCE_MULTI = 16
+OP_COSFEAT = 17
+COSFEAT_MAX_TAPS = 8
 (ATTN_L2NORM, ATTN_L2NORM_BWD, ATTN_CORR, ATTN_GATHER, ATTN_GATHER_T, ATTN_SOFTMAX, ATTN_SOFTMAX_BWD, ATTN_WNORM,
  ATTN_WNORM_BWD, ATTN_POOL, ATTN_POOL_T) = range(11)
 
@@ -171,6 +173,24 @@ class SynthScoreDesc(ctypes.Structure):
     ]
 
 
+class SynthVggLoadDesc(ctypes.Structure):
+    _fields_ = [
+        ("pred", vp), ("gt", vp), ("out", vp), ("lut", vp),
+        ("pred_s0", i64), ("pred_s1", i64), ("gt_s0", i64), ("gt_s1", i64),
+        ("n0", i32), ("n1", i32), ("h", i32), ("w", i32), ("h16", i32), ("w16", i32), ("dtype", i32),
+        ("img0", i32), ("n_out", i32), ("pad0", i32),
+    ]
+
+
+class CosFeatDesc(ctypes.Structure):
+    _fields_ = [
+        ("feat", vp), ("ws", vp), ("out", vp), ("ld", i64),
+        ("mode", i32), ("dtype", i32), ("n", i32), ("h", i32), ("w", i32), ("c", i32),
+        ("tap", i32), ("n_taps", i32), ("ws_blocks", i32), ("pad0", i32),
+        ("blocks", i32 * COSFEAT_MAX_TAPS), ("px", i32 * COSFEAT_MAX_TAPS),
+    ]
+
+
 class BnDesc(ctypes.Structure):
     _fields_ = [
         ("x", vp), ("y", vp), ("g", vp), ("dx", vp), ("gamma", vp), ("beta", vp), ("dgamma", vp), ("dbeta", vp),
@@ -263,7 +283,7 @@ class _OpUnion(ctypes.Union):
         ("conv", ConvDesc), ("wgrad", WgradDesc), ("wreduce", WreduceDesc), ("colsum", ColsumDesc),
         ("ew", EwDesc), ("loss", LossDesc), ("pack", PackList), ("bn", BnDesc), ("head", HeadDesc),
         ("attn", AttnDesc), ("head3", Head3BwdDesc), ("segenc", SegencDesc), ("segenc_bwd", SegencBwdDesc),
-        ("wreduce_multi", WreduceMultiDesc),
+        ("wreduce_multi", WreduceMultiDesc), ("cosfeat", CosFeatDesc),
     ]
 
 
@@ -273,9 +293,10 @@ class Op(ctypes.Structure):
 
 _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, OP_COLSUM: ColsumDesc,
         OP_EW: EwDesc, OP_LOSS: LossDesc, OP_PACK: PackDesc, OP_BN_FWD: BnDesc, OP_HEAD_FWD: HeadDesc,
-        OP_ATTN: AttnDesc, OP_HEAD3_BWD: Head3BwdDesc, OP_SEGENC_FWD: SegencDesc, OP_SEGENC_BWD: SegencBwdDesc, OP_WREDUCE_MULTI: WreduceMultiDesc, 100: WarpDesc, 101: SoftmaxDesc, 102: SnLayer, 103: ClipDesc,
+        OP_ATTN: AttnDesc, OP_HEAD3_BWD: Head3BwdDesc, OP_SEGENC_FWD: SegencDesc, OP_SEGENC_BWD: SegencBwdDesc, OP_WREDUCE_MULTI: WreduceMultiDesc,
+        OP_COSFEAT: CosFeatDesc, 100: WarpDesc, 101: SoftmaxDesc, 102: SnLayer, 103: ClipDesc,
         104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc, 107: SynthScoreDesc,
-        108: SynthLoadPadDesc, 109: SynthFinishCropDesc}
+        108: SynthLoadPadDesc, 109: SynthFinishCropDesc, 110: SynthVggLoadDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -288,6 +309,7 @@ EXPORTS = [
     "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_pack_blocks", "dvie_trace_kernels", "dvie_traced_kernels",
     "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_score_ws_bytes",
     "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits", "dvie_bn_partial_doubles",
+    "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks",
 ]
 
 _lib = None
@@ -323,7 +345,8 @@ def load():
                      "dvie_loss", "dvie_warp_fwd", "dvie_warp_bwd", "dvie_bn_fwd", "dvie_bn_bwd", "dvie_head_fwd",
                      "dvie_head_bwd", "dvie_softmax_fwd", "dvie_softmax_bwd", "dvie_clip_prep", "dvie_attn",
                      "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
-                     "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop"):
+                     "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop",
+                     "dvie_synth_vgg_load", "dvie_cosfeat"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]
@@ -334,7 +357,7 @@ def load():
         lib.dvie_traced_kernels.argtypes = []
         lib.dvie_traced_kernels.restype = ctypes.c_char_p
         for name in ("dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_bn_partial_splits", "dvie_pack_blocks",
-                     "dvie_conv_zbits"):
+                     "dvie_conv_zbits", "dvie_cosfeat_blocks"):
             getattr(lib, name).argtypes = [vp]
             getattr(lib, name).restype = i32
         lib.dvie_run_ops.argtypes = [vp, i32, vp]

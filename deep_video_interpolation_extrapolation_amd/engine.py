@@ -1,7 +1,7 @@
 """Plan compiler for the MI355X frame-synthesis path.
 
 A network (HRNet coarse generator, VGG19 perceptual features, ...) is described once with
-a small builder API (`Graph.conv / fuse / pool / input_nchw / l1feat`).  `Graph.compile`
+a small builder API (`Graph.conv / fuse / pool / input_nchw / l1feat / cosfeat`).  `Graph.compile`
 turns it into two flat descriptor lists for the C ABI (include/dvie.h):
 
 * forward:  weight packing (one launch for all layers) + one descriptor per op;
@@ -381,6 +381,17 @@ class L1FeatOp(_Op):
         return [self.a]
 
 
+class CosFeatOp(_Op):
+    """per-image cosine partials of a feature buffer holding [pred batch | gt batch]: tap `idx`
+    of the per-frame perceptual score (dvie_cosfeat).  Forward only."""
+
+    def __init__(self, a, idx):
+        self.a, self.idx, self.out, self.act = a, idx, None, L.ACT_NONE
+
+    def inputs(self):
+        return [self.a]
+
+
 class BNOp(_Op):
     """BatchNorm2d (+ activation) of a conv output buffer (reference nn.BatchNorm2d in
     nets/FrameDisc.py / nets/VidDisc.py / VAEHRNet).  x must be read by this op only."""
@@ -441,6 +452,7 @@ class Graph:
         self.segenc = []  # ConvOp triples marked by segenc_chain
         self.bn_training = True  # owners set it to their module's training flag
         self.n_l1 = 0
+        self.n_cos = 0  # cosfeat taps (the plan appends their finalize launch as its last op)
 
     # ---------------- builder ----------------
     def buffer(self, name, H, W, C, dtype=None, external=False):
@@ -585,6 +597,15 @@ class Graph:
         self.n_l1 += 1
         self._add(op)
         return op.idx
+
+    def cosfeat(self, region, idx):
+        """tap `idx` of the per-frame feature-cosine score: `region` (the batch [pred | gt]) is
+        reduced to per-image partials right after its producer, so an arena closes the tap's
+        lifetime there; the plan's last op averages the taps (Plan.set_cosfeat).  Forward only."""
+        assert idx == self.n_cos < L.COSFEAT_MAX_TAPS, (idx, self.n_cos)
+        self.n_cos += 1
+        self._add(CosFeatOp(region, idx))
+        return idx
 
     def output(self, key, region, channels):
         self.outputs[key] = (region, channels)
@@ -746,6 +767,8 @@ class Plan:
         self.fwd_off = self.n_bwd = 0
         self._l1_fwd = []  # (forward list index, level) of the VGG feature-L1 loss ops
         self._l1_bwd = []  # (backward index, seed scale) of their gradient seeds
+        self._cos_fwd = []  # (forward list index, tap, blocks per image, pixels) of the cosfeat ops, the finalize last
+        self.cos_ws_blocks = 0  # partial-workspace row length of the cosfeat taps (set_cosfeat)
         self.ext_in = {}  # key -> list of (op index, InputOp) for patching
         self.ext_out = {}
         self.ext_mask = {}  # key -> list of ('fwd'|'bwd', op index, MaskOp)
@@ -1052,6 +1075,8 @@ class Plan:
             if lower is None:
                 raise TypeError(site[0])
             lower(self, site[0])
+        if self._cos_fwd:
+            self._cosfeat_finalize()
 
     def _label_input_fwd(self, op):
         o = self.ew_desc(L.EW_LABELS, self.nf, op.out.H, op.out.W, op.out.c, self.ptr(op.out), op.out.buf.C)
@@ -1173,6 +1198,37 @@ class Plan:
         d.partial = part.data_ptr()
         d.out = self.l1_out.data_ptr() + 4 * op.idx
         self._l1_fwd.append((len(self.fwd), op.idx))
+        self.fwd.append(o)
+
+    def _cosfeat_fwd(self, op):
+        assert not self.backward_enabled, "cosfeat is a forward-only op (the per-frame score has no gradient)"
+        a, half = op.a, self.nf // 2
+        assert self.nf == 2 * half, "cosfeat compares image i with image nf / 2 + i"
+        o = self._op(L.OP_COSFEAT)
+        d = o.u.cosfeat
+        d.feat, d.ld = self.ptr(a), a.buf.C
+        d.mode, d.dtype, d.n, d.h, d.w, d.c = 0, dv_dtype(a.buf.dt), half, a.H, a.W, a.c
+        d.tap, d.n_taps = op.idx, self.g.n_cos
+        blocks = L.load().dvie_cosfeat_blocks(ctypes.byref(d))
+        if blocks < 1:
+            raise ValueError(f"cosfeat: no kernel for a {a.H}x{a.W}x{a.c} {a.buf.dt} feature map")
+        npx = self.nf * a.H * a.W
+        o.meta = dict(cls="cosfeat", name=f"cosfeat{op.idx} {self.nf}x{a.H}x{a.W}x{a.c}", flops=6.0 * npx * a.c,
+                      bytes=float(elem_size(a.buf.dt) * npx * a.c))
+        self._cos_fwd.append((len(self.fwd), op.idx, blocks, a.H * a.W))
+        self.fwd.append(o)
+
+    def _cosfeat_finalize(self):
+        """the plan's last op: one launch averages the taps' partials into one float64 per image"""
+        o = self._op(L.OP_COSFEAT)
+        d = o.u.cosfeat
+        d.mode, d.n, d.n_taps = 1, self.nf // 2, self.g.n_cos
+        for _, idx, blocks, px in self._cos_fwd:
+            d.blocks[idx], d.px[idx] = blocks, px
+        self.cos_ws_blocks = max(b for _, _, b, _ in self._cos_fwd)
+        o.meta = dict(cls="cosfeat", name="cosfeat finalize", flops=0.0,
+                      bytes=8.0 * (self.nf // 2) * sum(b for _, _, b, _ in self._cos_fwd))
+        self._cos_fwd.append((len(self.fwd), None, 0, 0))
         self.fwd.append(o)
 
     # ---------------- local-window attention ----------------
@@ -1956,7 +2012,7 @@ class Plan:
     # graph op type -> its lowering, per direction
     _FWD = {LabelInputOp: _label_input_fwd, InputOp: _input_fwd, ConvOp: _conv_fwd, ConvTOp: _convT_fwd,
             AttnOp: _attn_fwd, FuseOp: _fuse_fwd, MaskOp: _mask_fwd, OutNCHWOp: _out_nchw_fwd, PoolOp: _pool_fwd,
-            BNOp: _bn_fwd, HeadOp: _head_fwd, L1FeatOp: _l1feat_fwd}
+            BNOp: _bn_fwd, HeadOp: _head_fwd, L1FeatOp: _l1feat_fwd, CosFeatOp: _cosfeat_fwd}
     _BWD = {LabelInputOp: _input_backward, InputOp: _input_backward, ConvOp: _conv_backward, ConvTOp: _convT_backward,
             AttnOp: _attn_backward, FuseOp: _fuse_backward, MaskOp: _mask_backward, OutNCHWOp: _out_nchw_backward,
             PoolOp: _pool_backward, BNOp: _bn_backward, HeadOp: _head_backward, L1FeatOp: _l1feat_backward}
@@ -2232,6 +2288,20 @@ class Plan:
                 d.out, d.out_acc, d.out_scale = out.data_ptr(), int(k > 0), value_scale / nl
         for i, base in self._l1_bwd:
             self.bwd_arr[i].u.ew.scale = base * grad_scale
+
+    @property
+    def cosfeat_ws_doubles(self):
+        """float64 elements of the partial workspace set_cosfeat takes"""
+        return self.g.n_cos * (self.nf // 2) * self.cos_ws_blocks
+
+    def set_cosfeat(self, ws, out):
+        """Where the cosfeat taps put their partials (`ws`: cosfeat_ws_doubles float64, fully
+        rewritten by a forward) and the last op its per-image scores (`out`: nf / 2 float64)."""
+        assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= self.cosfeat_ws_doubles
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == self.nf // 2
+        for idx, *_ in self._cos_fwd:
+            d = self.fwd_arr[idx + self.fwd_off].u.cosfeat
+            d.ws, d.out, d.ws_blocks = ws.data_ptr(), out.data_ptr(), self.cos_ws_blocks
 
     def set_input_grad(self, key, t, accumulate=False):
         for idx, op in self.ext_grad[key]:

@@ -115,7 +115,51 @@ class my_vgg(nn.Module):
                 x = E.R(b)
         return feats
 
+    def lower_score(self, g, H, W):
+        """Scoring graph (synth.PerceptualScorer): `vgg_in` (2n images [pred | gt], already
+        normalised) is written by the caller (dvie_synth_vgg_load into plan.input_view("vgg_in"));
+        convs, pools and one cosfeat per tap right after the tap's conv.  No input op, no
+        feature-L1, no backward.  H and W are multiples of 16 (synth.vgg_region)."""
+        assert H % 16 == 0 and W % 16 == 0 and H >= 16 and W >= 16, (H, W)
+        inp = g.buffer("vgg_in", H, W, 8)
+        x = g.caller_input(E.R(inp), "vgg_in")
+        feats = []
+        h, w = H, W
+        for i, m in enumerate(self.vgg.features):
+            if i > 35:
+                break
+            if isinstance(m, nn.Conv2d):
+                b = g.buffer(f"vgg{i}", h, w, m.out_channels)
+                g.conv(x, m, E.R(b), act=L.ACT_RELU, trainable=False, name=f"features.{i}")
+                x = E.R(b)
+                if i + 1 in FEATURE_TAPS:
+                    g.cosfeat(x, len(feats))
+                    feats.append(x)
+            elif isinstance(m, nn.MaxPool2d) and i < 35:
+                h, w = h // 2, w // 2
+                b = g.buffer(f"vgg{i}", h, w, x.c)
+                g.pool(x, E.R(b))
+                x = E.R(b)
+        return feats
+
+    def score_plan(self, n, H, W, dev, alias=True):
+        """the pooled scoring plan of n frame pairs of (H, W), in the process precision; its pool
+        key ("score", ...) keeps it apart from the loss and feature plans.  alias=False gives
+        every activation a buffer of its own (the arena's reference in the tests)."""
+        return self._pool.acquire(("score", n, H, W, self.dtype, dev, bool(alias)))
+
+    def _build_score_plan(self, key):
+        _, n, H, W, dtype, dev, alias = key
+        g = E.Graph(dtype)
+        feats = self.lower_score(g, H, W)
+        plan = g.compile(2 * n, dev, backward=False, alias=alias)
+        plan.static_weights = True  # as the loss plan: the weights are packed once
+        plan.feats = feats
+        return plan
+
     def _build_plan(self, key):
+        if key[0] == "score":
+            return self._build_score_plan(key)
         n, H, W, dtype, normalize, loss, dev = key
         g = E.Graph(dtype)
         feats = self.lower(g, H, W, normalize, loss)

@@ -16,6 +16,10 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
                             frames from a clip's first two and scores them against the frames that
                             follow.  Writes <cycgen_load_dir>/synth_eval/scores.json (per clip and slot
                             PSNR, SSIM, label accuracy, mIoU; the mean summary), no PNGs
+  --synth_vgg               with --synth_eval: also the per-frame VGG19 perceptual score (the reference's
+                            `vgg` validation metric, synth.PerceptualScorer) -> "vgg" per clip and in the
+                            summary of scores.json, and "vgg_weights"; taken on the top-left
+                            (H // 16 * 16, W // 16 * 16) of the frames, which must be at least 16x16
   --synth_pad {none,replicate}
                             --split test: `none` takes only clips whose height and width are multiples
                             of the net's coarsest stride (4; 8 with --highres_large; 4 << (--n_sc - 1)
@@ -77,6 +81,7 @@ GLOBAL = [
     ("--clip_store", "clip_store", str, None, None),
     ("--synth_levels", "synth_levels", int, 1, None),
     ("--synth_eval", "synth_eval", bool, False, None),
+    ("--synth_vgg", "synth_vgg", bool, False, None),
     ("--synth_pad", "synth_pad", str, "none", ["none", "replicate"]),
 ]
 

@@ -402,9 +402,10 @@ class InterTrainer:
                     Image.fromarray(np.ascontiguousarray(arr[k])).save(os.path.join(d, "{:04d}.png".format(k)))
         return root
 
-    def _score(self, syn, frames, labels, clip):
+    def _score(self, syn, frames, labels, clip, perceptual=None):
         """--split test --synth_eval, interpolation: every 2**synth_levels-th frame is kept, the
-        others are synthesised and scored (None: the clip is too short)"""
+        others are synthesised and scored (None: the clip is too short); perceptual: the
+        PerceptualScorer of --synth_vgg"""
         step = 1 << getattr(self.args, "synth_levels", 1)
         T = frames.shape[1]
         keep = (T - 1) // step * step + 1
@@ -413,7 +414,8 @@ class InterTrainer:
             return None
         if keep < T:
             self.log.info(f"synth_eval: {clip}: the last {T - keep} of {T} frames dropped ((T - 1) % {step} != 0)")
-        return syn.score_interpolation(frames[:, :keep], labels[:, :keep], levels=getattr(self.args, "synth_levels", 1))
+        return syn.score_interpolation(frames[:, :keep], labels[:, :keep], levels=getattr(self.args, "synth_levels", 1),
+                                       perceptual=perceptual)
 
     def test_eval(self):
         """--split test --synth_eval: the clips of test(), scored instead of written.  Per clip
@@ -421,14 +423,19 @@ class InterTrainer:
         held-out frames -> <cycgen_load_dir>/synth_eval/scores.json: {"clips": {clip: {"slots",
         "psnr", "ssim", "acc", "miou"}} (one value per scored slot), "summary": the means over
         every scored frame of every clip and per position (synth.summarize)}; the summary also
-        goes to the log.  No PNG is written."""
+        goes to the log.  No PNG is written.  With --synth_vgg one synth.PerceptualScorer scores
+        every clip too: "vgg" per clip, in the summary and in every per_position row, and a
+        top-level "vgg_weights" naming the VGG19 weights (PerceptualScorer.weights_name); a clip
+        whose size is no multiple of 16 is scored on synth.vgg_region of it (logged once per clip)."""
         import numpy as np
         from PIL import Image
-        from ..synth import summarize
+        from ..synth import PerceptualScorer, summarize, vgg_region
         a = self.args
         syn = self._synthesizer()
+        scorer = PerceptualScorer(max_batch=max(1, a.batch_size)) if getattr(a, "synth_vgg", False) else None
+        keys = ("psnr", "ssim", "acc", "miou") + (("vgg",) if scorer else ())
         img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
-        clips, cols = {}, [[] for _ in range(5)]
+        clips, cols = {}, [[] for _ in range(1 + len(keys))]
         for clip in sorted(d for d in os.listdir(img_dir) if os.path.isdir(os.path.join(img_dir, d))):
             names = sorted(f for f in os.listdir(os.path.join(img_dir, clip)) if f.lower().endswith(".png"))
             if not names:
@@ -436,15 +443,20 @@ class InterTrainer:
                 continue
             imgs = np.stack([np.asarray(Image.open(os.path.join(img_dir, clip, f)).convert("RGB")) for f in names])
             labs = np.stack([np.asarray(Image.open(os.path.join(seg_dir, clip, f)).convert("L")) for f in names])
+            if scorer and vgg_region(*imgs.shape[1:3]) != imgs.shape[1:3]:
+                self.log.info("synth_eval: {}: vgg is scored on the top-left {}x{} of the {}x{} frames".format(
+                    clip, *vgg_region(*imgs.shape[1:3]), *imgs.shape[1:3]))
             sc = self._on_clip(self._score, syn, torch.from_numpy(imgs)[None].to(self.device),
-                               torch.from_numpy(labs)[None].to(self.device), clip)
+                               torch.from_numpy(labs)[None].to(self.device), clip, scorer)
             if sc is None:
                 continue
-            vals = [v[0] for v in sc.host()]  # psnr, ssim, acc, miou of the one clip
-            clips[clip] = dict(slots=sc.slots, **{k: v.tolist() for k, v in zip(("psnr", "ssim", "acc", "miou"), vals)})
+            vals = [v[0] for v in sc.host(vgg=scorer is not None)]  # psnr, ssim, acc, miou (, vgg) of the one clip
+            clips[clip] = dict(slots=sc.slots, **{k: v.tolist() for k, v in zip(keys, vals)})
             for col, v in zip(cols, [np.asarray(sc.positions)] + vals):
                 col.append(v)
         res = dict(clips=clips, summary=summarize(*[np.concatenate(c) for c in cols]) if clips else None)
+        if scorer:
+            res["vgg_weights"] = scorer.weights_name
         root = os.path.join(a.cycgen_load_dir, "synth_eval")
         os.makedirs(root, exist_ok=True)
         with open(os.path.join(root, "scores.json"), "w") as f:

@@ -40,6 +40,11 @@ writes both canvases of an input slot (its last row and column repeated), and
 `dvie_synth_finish_crop` writes the cropped uint8 frame and label of a forward and, for a slot
 a later forward reads, the argmax over the whole canvas.  A prediction's pad region is the
 network's own output; the uint8 storage the caller gets stays (H, W).
+
+Scoring: `frame_scores` (PSNR, SSIM, label agreement: dvie_synth_score) and, opt-in,
+`PerceptualScorer`, the per-frame VGG19 feature cosine: `dvie_synth_vgg_load` fills the input
+buffer of my_vgg's forward-only, arena-allocated scoring plan from the uint8 frames, and the
+plan's own cosfeat ops reduce the five feature maps to one float64 per frame.
 """
 import ctypes
 
@@ -173,11 +178,12 @@ class FrameScores:
     shaped like the leading dimensions of the frames -- sse (int64), ssim (float64) and, with
     label maps, agree, valid (int64), inter, uni (int64, a trailing class dimension); None
     without.  psnr / acc / miou are derived on the device in float64."""
-    FIELDS = ("sse", "ssim", "agree", "valid", "inter", "uni")
+    FIELDS = ("sse", "ssim", "agree", "valid", "inter", "uni", "vgg")
 
-    def __init__(self, H, W, sse, ssim, agree=None, valid=None, inter=None, uni=None):
+    def __init__(self, H, W, sse, ssim, agree=None, valid=None, inter=None, uni=None, vgg=None):
         self.H, self.W = H, W
         self.sse, self.ssim, self.agree, self.valid, self.inter, self.uni = sse, ssim, agree, valid, inter, uni
+        self.vgg = vgg  # float64 VGG19 feature cosine per frame (frame_scores(..., perceptual=)), or None
 
     @property
     def psnr(self):
@@ -224,12 +230,158 @@ def _lead_of(t, tail, what):
     return n0, n1, s0, s1
 
 
-def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20):
+def vgg_region(H, W):
+    """The top-left region (H // 16 * 16, W // 16 * 16) of an (H, W) frame that the perceptual
+    score is taken on: the VGG plan's four 2x2 poolings need even sizes at every level.  When H
+    and W are multiples of 16 this is the whole frame; otherwise up to 15 trailing rows and
+    columns are not seen.  A side below 16 raises ValueError."""
+    if H < 16 or W < 16:
+        raise ValueError(f"the perceptual score needs frames of at least 16x16, got {H}x{W}")
+    return H // 16 * 16, W // 16 * 16
+
+
+def vgg_lut(dtype=torch.float32):
+    """The (3, 256) table of dvie_synth_vgg_load (a CPU tensor): lut[c][v] = (v / 255 - mean_c) /
+    std_c with the ImageNet constants, computed in float64 and rounded once to fp32; for
+    torch.bfloat16 that fp32 value rounded once more, to nearest even."""
+    import numpy as np
+    v = np.arange(256, dtype=np.float64)
+    t = torch.from_numpy(np.stack([np.float32((v / 255.0 - m) / s) for m, s in zip(E._IMAGENET_MEAN, E._IMAGENET_STD)]))
+    return t.bfloat16() if dtype == torch.bfloat16 else t
+
+
+def _vgg_load_call(pred, gt, n0, n1, strides, H, W, region, out, lut, img0, n_out):
+    d = L.SynthVggLoadDesc()
+    d.pred, d.gt, d.out, d.lut = pred, gt, out.data_ptr(), lut.data_ptr()
+    d.pred_s0, d.pred_s1, d.gt_s0, d.gt_s1 = strides
+    d.n0, d.n1, d.h, d.w = n0, n1, H, W
+    (d.h16, d.w16), d.dtype, d.img0, d.n_out = region, E.dv_dtype(out.dtype), img0, n_out
+    L.check(L.load().dvie_synth_vgg_load(ctypes.byref(d), L.stream_ptr(out.device)), "synth vgg_load")
+
+
+def _pairs_of(pred, gt):
+    """the checks frame_scores makes on its frames -> (lead, H, W, n0, n1, byte strides of pred and gt)"""
+    L.require_gpu(pred)
+    if pred.dim() < 3 or pred.shape[-1] != 3:
+        raise ValueError(f"pred: uint8 (..., H, W, 3), got {tuple(pred.shape)}")
+    lead, (H, W) = tuple(pred.shape[:-3]), pred.shape[-3:-1]
+    if H < 1 or W < 1 or any(n < 1 for n in lead):
+        raise ValueError(f"pred: empty dimensions in {tuple(pred.shape)}")
+    n0, n1, ps0, ps1 = _lead_of(pred, (H, W, 3), "pred")
+    if not isinstance(gt, torch.Tensor) or gt.device != pred.device or tuple(gt.shape[:gt.dim() - 3]) != lead:
+        raise ValueError(f"gt: a tensor on {pred.device} with the leading dimensions {lead} of pred")
+    _, _, gs0, gs1 = _lead_of(gt, (H, W, 3), "gt")
+    return lead, H, W, n0, n1, (ps0, ps1, gs0, gs1)
+
+
+def vgg_load(pred, gt, out, lut):
+    """uint8 frames `pred`, `gt` (..., H, W, 3) (up to two leading dimensions of any strides, as
+    frame_scores takes them) -> `out` (2n, h16, w16, 8), fp32 or bf16, contiguous: the images
+    [pred_0 .. pred_{n-1} | gt_0 .. gt_{n-1}] over the region vgg_region(H, W), channels 0-2
+    looked up in `lut` (vgg_lut(out.dtype) on the device), channels 3-7 zero (dvie_synth_vgg_load)."""
+    lead, H, W, n0, n1, strides = _pairs_of(pred, gt)
+    region = vgg_region(H, W)
+    assert out.is_contiguous() and tuple(out.shape) == (2 * n0 * n1,) + region + (8,), (out.shape, n0, n1, region)
+    assert lut.dtype == out.dtype and lut.is_contiguous() and tuple(lut.shape) == (3, 256) and lut.device == out.device
+    _vgg_load_call(pred.data_ptr(), gt.data_ptr(), n0, n1, strides, H, W, region, out, lut, 0, n0 * n1)
+    return out
+
+
+class PerceptualScorer:
+    """Per-frame VGG19 perceptual score of uint8 device frames: the reference's `vgg` validation
+    metric (losses.VGGCosineLoss -- the cosine between the five my_vgg feature maps relu1_2 ..
+    relu5_4 of a frame and of its original, averaged over pixels, then over the five maps), one
+    float64 per frame, higher is better, 1 for equal frames, with nothing leaving the device.
+
+    scorer(pred, gt): uint8 (..., H, W, 3) with up to two leading dimensions of any strides (what
+    frame_scores takes) -> a float64 device tensor shaped like the leading dimensions.  A pixel
+    whose feature vector is all zero on either side makes its frame's score NaN (the reference's
+    0/0) and no other frame's.
+
+    The score is taken on the top-left region vgg_region(H, W) = (H // 16 * 16, W // 16 * 16) of
+    both frames, read in place (no cropped copy): with H and W multiples of 16 it is the
+    reference's value on the whole frame; otherwise up to 15 trailing rows and columns are not
+    seen.  A side below 16 raises ValueError.
+
+    vgg_net: a nets.vgg.my_vgg already on the device (a trainer's, so that the weights are
+    shared); None builds one from vgg19_features() (DVIE_VGG19_WEIGHTS, or the seeded synthetic
+    weights) and moves it to the frames' device at the first call.  The VGG runs in the net's
+    precision (precision_of()).  max_batch: frame pairs per VGG forward.  The pairs are cut, in
+    order, into chunks of at most max_batch; every chunk size takes a pooled, arena-allocated
+    plan of its own, so a last smaller chunk compiles (once) a second plan.
+
+    Per chunk: dvie_synth_vgg_load writes the plan's input buffer, the plan runs its convs and
+    poolings with one cosine reduction per feature map, and its last op writes the chunk's
+    scores.  Everything runs on the caller's current stream and nothing synchronises with the
+    host; the partial workspace and the output are allocated per call on that stream, the
+    256-entry normalisation table once per device."""
+
+    def __init__(self, vgg_net=None, max_batch=8):
+        from .nets.vgg import my_vgg, vgg19_features
+        if vgg_net is not None and not isinstance(vgg_net, my_vgg):
+            raise ValueError(f"vgg_net: a nets.vgg.my_vgg, got {type(vgg_net).__name__}")
+        if max_batch < 1:
+            raise ValueError(f"max_batch={max_batch} must be at least 1")
+        self._own = vgg_net is None
+        self.net = my_vgg(vgg19_features()) if self._own else vgg_net
+        self.max_batch = int(max_batch)
+        self._lut = {}  # (device, dtype) -> the table on the device
+
+    @property
+    def weights_name(self):
+        """which weights the score was taken with: the basename of DVIE_VGG19_WEIGHTS or
+        "synthetic-seed19" (what scores.json records as vgg_weights)"""
+        import os
+        from .nets.vgg import SYNTH_SEED
+        path = os.environ.get("DVIE_VGG19_WEIGHTS")
+        return os.path.basename(path) if path else f"synthetic-seed{SYNTH_SEED}"
+
+    def _table(self, dev):
+        key = (dev, self.net.dtype)
+        if key not in self._lut:
+            self._lut[key] = vgg_lut(self.net.dtype).to(dev)
+        return self._lut[key]
+
+    def __call__(self, pred, gt):
+        lead, H, W, n0, n1, (ps0, ps1, gs0, gs1) = _pairs_of(pred, gt)
+        region = vgg_region(H, W)
+        dev = pred.device
+        if next(self.net.parameters()).device != dev:
+            if not self._own:
+                raise ValueError(f"vgg_net is on {next(self.net.parameters()).device}, the frames on {dev}")
+            self.net.to(dev)
+        if n1 == 1:  # (B, 1) views: one run of B pairs instead of B rows of one
+            n0, n1, ps0, ps1, gs0, gs1 = 1, n0, 0, ps0, 0, gs0
+        N = n0 * n1
+        lut = self._table(dev)
+        out = torch.empty((N,), dtype=torch.float64, device=dev)
+        with torch.no_grad():
+            for f0 in range(0, N, self.max_batch):
+                f1 = min(N, f0 + self.max_batch)
+                plan = self.net.score_plan(f1 - f0, region[0], region[1], dev)
+                view = plan.input_view("vgg_in")
+                f = f0
+                while f < f1:  # the chunk's pairs, row by row of the (n0, n1) frame grid
+                    i0, a = divmod(f, n1)
+                    b = min(n1, a + f1 - f)
+                    _vgg_load_call(pred.data_ptr() + i0 * ps0 + a * ps1, gt.data_ptr() + i0 * gs0 + a * gs1, 1, b - a,
+                                   (0, ps1, 0, gs1), H, W, region, view, lut, f - f0, f1 - f0)
+                    f += b - a
+                ws = torch.empty((plan.cosfeat_ws_doubles,), dtype=torch.float64, device=dev)
+                plan.set_cosfeat(ws, out[f0:f1])
+                plan.run_forward()
+        return out.reshape(lead)
+
+
+def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perceptual=None):
     """Score uint8 device frames `pred` (..., H, W, 3) against `gt` and, when both are given,
     label maps `pred_labels` (..., H, W) against `gt_labels` (dvie_synth_score: one fused pass
     and a finalize launch, no host synchronisation) -> FrameScores shaped like the leading
     dimensions.  Up to two leading dimensions, of any strides (the (B, S) views interpolate /
-    extrapolate return are scored in place); the frame-level dimensions must be contiguous."""
+    extrapolate return are scored in place); the frame-level dimensions must be contiguous.
+    perceptual: a PerceptualScorer -> the result also has `.vgg`, the per-frame VGG19 feature
+    cosine on the region vgg_region(H, W) (up to 15 trailing rows and columns are not seen when
+    H or W is no multiple of 16; a side below 16 raises ValueError); None: `.vgg` is None."""
     L.require_gpu(pred)
     if pred.dim() < 3 or pred.shape[-1] != 3:
         raise ValueError(f"pred: uint8 (..., H, W, 3), got {tuple(pred.shape)}")
@@ -241,6 +393,8 @@ def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20):
     has_labels = pred_labels is not None
     if has_labels and not 1 <= n_classes <= 32:
         raise ValueError(f"n_classes={n_classes} must be in 1..32")
+    if perceptual is not None:
+        vgg_region(H, W)  # (a frame too small for the perceptual score fails before anything runs)
     d = L.SynthScoreDesc()
     d.n0, d.n1, d.pred_s0, d.pred_s1 = _lead_of(pred, (H, W, 3), "pred")
     for t, tail, what in ((gt, (H, W, 3), "gt"),) + (((pred_labels, (H, W), "pred_labels"),
@@ -264,18 +418,23 @@ def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20):
     ws = torch.empty((lib.dvie_synth_score_ws_bytes(ctypes.byref(d)),), dtype=torch.uint8, device=dev)
     d.ws = ws.data_ptr()
     L.check(lib.dvie_synth_score(ctypes.byref(d), L.stream_ptr(dev)), "synth score")
+    if perceptual is not None:
+        out.vgg = perceptual(pred, gt)
     return out
 
 
-def summarize(position, psnr, ssim, acc, miou):
+def summarize(position, psnr, ssim, acc, miou, vgg=None):
     """Host-side means of per-frame scores (numpy arrays of one length; `position` an integer
     per frame) -> {"psnr", "ssim", "acc", "miou", "frames", "per_position": {position: the same
     four and "frames"}} as Python floats.  The mean PSNR is the mean of the per-frame PSNRs
-    (losses.py:103-116); an infinite value stays infinite."""
+    (losses.py:103-116); an infinite value stays infinite.  With `vgg` (the per-frame perceptual
+    scores) the result and every per_position row also have "vgg"."""
     import numpy as np
     position = np.asarray(position)
     cols = dict(psnr=np.asarray(psnr, dtype=np.float64), ssim=np.asarray(ssim, dtype=np.float64),
                 acc=np.asarray(acc, dtype=np.float64), miou=np.asarray(miou, dtype=np.float64))
+    if vgg is not None:
+        cols["vgg"] = np.asarray(vgg, dtype=np.float64)
 
     def means(sel):
         with np.errstate(invalid="ignore"):
@@ -292,7 +451,8 @@ class SynthScores:
     """What score_interpolation / score_extrapolation return: `slots`, the scored time indices
     (interpolation: indices into the clip; extrapolation: the step index k of original frame
     2 + k); `scores`, the FrameScores of shape (B, len(slots)), whose tensors and derived
-    values are also attributes here (sse, ssim, agree, valid, inter, uni, psnr, acc, miou);
+    values are also attributes here (sse, ssim, agree, valid, inter, uni, psnr, acc, miou, and
+    vgg when a PerceptualScorer was passed);
     `frames` / `labels`, the synthesised video as interpolate / extrapolate returns it;
     `positions`, per slot the position the summary groups by (slot % 2**levels, or the step)."""
 
@@ -304,18 +464,21 @@ class SynthScores:
             return getattr(self.scores, name)
         raise AttributeError(name)
 
-    def host(self):
-        """psnr, ssim, acc, miou as float64 numpy arrays (B, len(slots)): one copy to the host"""
+    def host(self, vgg=False):
+        """psnr, ssim, acc, miou -- with vgg=True also vgg (scored with a PerceptualScorer) -- as
+        float64 numpy arrays (B, len(slots)): one copy to the host"""
         s = self.scores
-        return tuple(torch.stack([s.psnr, s.ssim, s.acc, s.miou]).cpu().numpy())
+        if vgg and s.vgg is None:
+            raise ValueError("these scores have no vgg column (score_* was called without perceptual=)")
+        return tuple(torch.stack([s.psnr, s.ssim, s.acc, s.miou] + ([s.vgg] if vgg else [])).cpu().numpy())
 
     def summary(self):
         """Means over all scored frames and per position (summarize) as Python floats -- the
-        one place that copies to the host."""
+        one place that copies to the host.  "vgg" is included when the scores have it."""
         import numpy as np
-        psnr, ssim, acc, miou = self.host()
-        pos = np.broadcast_to(np.asarray(self.positions), psnr.shape)
-        return summarize(pos.ravel(), psnr.ravel(), ssim.ravel(), acc.ravel(), miou.ravel())
+        cols = self.host(vgg=self.scores.vgg is not None)
+        pos = np.broadcast_to(np.asarray(self.positions), cols[0].shape)
+        return summarize(pos.ravel(), *[c.ravel() for c in cols])
 
 
 class FrameSizeError(ValueError):
@@ -614,34 +777,43 @@ class VideoSynthesizer:
         return fr[2:].transpose(0, 1), lb[2:].transpose(0, 1)
 
     # ---------------- held-out scoring ----------------
-    def score_interpolation(self, frames, labels, levels=1):
+    def score_interpolation(self, frames, labels, levels=1, perceptual=None):
         """Held-out scoring of interpolation: frames (B, T, H, W, 3) and labels (B, T, H, W) of
         real clips with (T - 1) % 2**levels == 0 and T > 2**levels.  Frames 0, 2**levels, ...
         go through interpolate(..., levels); every other slot t is scored against original
         frame and label map t (heldout_slots) -> SynthScores, tensors (B, len(slots)).  The
         slots at one offset inside the period are one strided (B, G) view of the synthesised
-        and of the original video, scored in place: 2**levels - 1 scoring calls."""
+        and of the original video, scored in place: 2**levels - 1 scoring calls.
+        perceptual: a PerceptualScorer -> the scores also have `.vgg` (frame_scores)."""
         self._check(frames, labels)
+        if perceptual is not None:
+            vgg_region(*frames.shape[2:4])  # (too small a frame fails before the synthesis runs)
         T, step = frames.shape[1], 1 << max(levels, 0)
         slots = heldout_slots(T, levels)
         out_f, out_l = self.interpolate(frames[:, ::step], labels[:, ::step], levels)
         parts = [frame_scores(out_f[:, o::step], frames[:, o::step], out_l[:, o::step], labels[:, o::step],
-                              n_classes=self.cm.n_classes) for o in range(1, step)]
+                              n_classes=self.cm.n_classes, perceptual=perceptual) for o in range(1, step)]
         # (B, G) per offset -> (B, G, step - 1) -> (B, G * (step - 1)): ascending slots
         scores = parts[0].map(lambda _: None)
         for k in FrameScores.FIELDS:
+            if getattr(parts[0], k) is None:  # (vgg without a scorer)
+                continue
             t = torch.stack([getattr(p, k) for p in parts], dim=2)
             setattr(scores, k, t.reshape((t.shape[0], len(slots)) + tuple(t.shape[3:])))
         return SynthScores(slots, [t % step for t in slots], scores, out_f, out_l)
 
-    def score_extrapolation(self, frames, labels):
+    def score_extrapolation(self, frames, labels, perceptual=None):
         """Held-out scoring of extrapolation: frames (B, 2 + S, H, W, 3), S >= 1.  The first two
         frames are the inputs of extrapolate(..., steps=S); step k is scored against original
-        frame 2 + k -> SynthScores with slots 0 .. S-1, tensors (B, S)."""
+        frame 2 + k -> SynthScores with slots 0 .. S-1, tensors (B, S).
+        perceptual: a PerceptualScorer -> the scores also have `.vgg` (frame_scores)."""
         self._check(frames, labels)
+        if perceptual is not None:
+            vgg_region(*frames.shape[2:4])
         S = frames.shape[1] - 2
         if S < 1:
             raise ValueError("score_extrapolation needs two input frames and at least one frame of truth")
         out_f, out_l = self.extrapolate(frames[:, :2], labels[:, :2], steps=S)
-        scores = frame_scores(out_f, frames[:, 2:], out_l, labels[:, 2:], n_classes=self.cm.n_classes)
+        scores = frame_scores(out_f, frames[:, 2:], out_l, labels[:, 2:], n_classes=self.cm.n_classes,
+                              perceptual=perceptual)
         return SynthScores(range(S), range(S), scores, out_f, out_l)

@@ -742,6 +742,48 @@ int dvie_segenc_bwd(const dvie_segenc_bwd_desc* d, void* stream);
 #define DVIE_OP_SEGENC_FWD 14
 #define DVIE_OP_SEGENC_BWD 15
 #define DVIE_OP_WREDUCE_MULTI 16
+#define DVIE_OP_COSFEAT 17
+
+/*
+ * dvie_cosfeat: per-image cosine similarity of VGG feature maps, the reduction behind the
+ * per-frame perceptual score (synth.PerceptualScorer; Graph.cosfeat in the plan engine).
+ *
+ * feat: NHWC feature maps (2n, h, w, c) of element type dtype with channel pitch ld (elements):
+ * image i (a prediction) is compared with image n + i (its original).  A score is
+ *
+ *   out[i] = (1 / n_taps) * sum over taps t of  mean over the tap's pixels of
+ *              dot(a, b) / (sqrtf(|a|^2) * sqrtf(|b|^2))          a, b the pixel's c channels
+ *
+ * with dot, |a|^2, |b|^2 summed in fp32 (DVIE_LOSS_COSNHWC's expression), the cosine formed in
+ * fp32 and every sum over pixels, blocks and taps in float64.  A pixel whose vector is all zero
+ * on either side is 0/0 = NaN and makes out[i] NaN, and no other image's value.
+ *
+ * mode 0 (one call per tap, after the tap is written): every block of tap `tap` writes its float64
+ *   partial to ws[(tap * n + i) * ws_blocks + block]; a block covers pixels of ONE image.
+ *   dvie_cosfeat_blocks(d) (from h, w, c, dtype) is the tap's block count per image, 0 for sizes
+ *   the kernel does not take: c must be a power-of-two number of 16-byte vectors (8 bf16 or 4
+ *   fp32 channels: 64, 128, 256, 512 ...), h * w < 2^30.  feat 16-byte aligned, ld >= c,
+ *   ld * sizeof(element) % 16 == 0: the loads are 16-byte vectors along the channels.
+ * mode 1 (once, after every tap): one block per image sums tap t's blocks[t] partials in index
+ *   order through a fixed tree, divides by px[t] (the tap's h * w), averages the n_taps taps and
+ *   writes out[i].  No atomics anywhere: two runs give the same bits.
+ * ws: n_taps * n * ws_blocks doubles, 8-byte aligned, ws_blocks >= every tap's block count; the
+ * entries read are all written by the mode-0 calls.  n <= 32767, n_taps <= DVIE_COSFEAT_MAX_TAPS.
+ */
+#define DVIE_COSFEAT_MAX_TAPS 8
+
+typedef struct dvie_cosfeat_desc {
+  const void* feat; /* mode 0 */
+  double* ws;
+  double* out; /* mode 1: n values */
+  long long ld;
+  int mode, dtype, n, h, w, c, tap, n_taps, ws_blocks, pad0;
+  int blocks[DVIE_COSFEAT_MAX_TAPS]; /* mode 1: per tap, its blocks per image ... */
+  int px[DVIE_COSFEAT_MAX_TAPS];     /* ... and its pixels per image */
+} dvie_cosfeat_desc;
+
+int dvie_cosfeat_blocks(const dvie_cosfeat_desc* d);
+int dvie_cosfeat(const dvie_cosfeat_desc* d, void* stream);
 
 typedef struct dvie_pack_list {
   const dvie_pack_desc* descs_dev;
@@ -766,6 +808,7 @@ typedef struct dvie_op {
     dvie_segenc_desc segenc;
     dvie_segenc_bwd_desc segenc_bwd;
     dvie_wreduce_multi_desc wreduce_multi;
+    dvie_cosfeat_desc cosfeat;
   } u;
 } dvie_op;
 
@@ -964,11 +1007,42 @@ typedef struct dvie_synth_score_desc {
 size_t dvie_synth_score_ws_bytes(const dvie_synth_score_desc* d);
 int dvie_synth_score(const dvie_synth_score_desc* d, void* stream);
 
+/*
+ * dvie_synth_vgg_load: uint8 frame pairs -> the input buffer of the VGG19 scoring plan
+ * (synth.PerceptualScorer).  Frames are addressed as dvie_synth_score addresses them: N = n0 * n1
+ * pairs, frame (i0, i1) at base + i0*s0 + i1*s1 BYTES, a frame a contiguous h*w*3 block of uint8
+ * RGB, no alignment assumed.  Only the top-left region (h16, w16) <= (h, w) of every frame is
+ * read, in place through the row pitch 3 * w (the plan's 2x2 poolings need multiples of 16:
+ * synth.vgg_region).  out: (2N, h16, w16, 8) contiguous, element type dtype, 16-byte aligned,
+ * images [pred_0 .. pred_{N-1} | gt_0 .. gt_{N-1}] (img0 = 0, n_out = N).  A call may also fill a
+ * part of a larger batch: with n_out > N the buffer holds 2 * n_out images and this call's pair j
+ * goes to images img0 + j and n_out + img0 + j (0 <= img0, img0 + N <= n_out).
+ *
+ *   out[img][y][x][c] = lut[c * 256 + byte]   c < 3
+ *                     = 0                      c = 3 .. 7 (written every time)
+ *
+ * lut: 3 x 256 elements of dtype on the device; the host computes (v / 255 - mean_c) / std_c in
+ * float64, rounds it once to fp32 and, for DVIE_BF16, that fp32 once more to bf16 (nearest even),
+ * so the device divides and rounds nothing and the result is defined bit for bit.
+ * n0 * n1 <= 32767, h16 * w16 < 2^31 - 256.
+ */
+typedef struct dvie_synth_vgg_load_desc {
+  const uint8_t* pred;
+  const uint8_t* gt;
+  void* out;
+  const void* lut;
+  long long pred_s0, pred_s1, gt_s0, gt_s1; /* byte strides of (i0, i1) */
+  int n0, n1, h, w, h16, w16, dtype;
+  int img0, n_out, pad0; /* pair j goes to images img0 + j and n_out + img0 + j of out (2 * n_out images) */
+} dvie_synth_vgg_load_desc;
+
+int dvie_synth_vgg_load(const dvie_synth_vgg_load_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
- * synth_bridge, synth_score, synth_load_pad, synth_finish_crop). */
+ * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

@@ -27,7 +27,16 @@
   of a 1080x1920 clip with pad="replicate" against the aligned path on the same clip padded to
   1088x1920 beforehand, alternating in one process, with the differing bytes of the two results.
 
-    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json] [--two-stage | --score | --pad]
+* the perceptual score (--vgg): us per call of synth.PerceptualScorer on uint8 frames (a) against
+  what there was before it for per-frame values (b: per frame, torch uint8 -> fp32 NCHW / 255, then
+  losses.VGGCosineLoss at batch 1) and against that composition at the full batch (c: one batch
+  mean only, for context), 8 pairs at 256x512 and 1 pair at 1024x2048, bf16, rotating over buffer
+  sets that exceed the Infinity Cache, the legs alternating, three rounds; per-op device times of
+  one scoring call (load, convs, poolings, cosine reductions, finalize) from events, with the
+  algorithmic GB/s of the load and cosine kernels; arena against one buffer per activation; and
+  one batch-8 forward for scale.
+
+    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json] [--two-stage | --score | --pad | --vgg]
 """
 import argparse
 import json
@@ -229,6 +238,116 @@ def score_numbers(dev, seconds):
     return out
 
 
+def vgg_arena_numbers():
+    """the scoring plan of my_vgg in bf16: arena against one buffer per activation (computed,
+    nothing allocated)"""
+    from deep_video_interpolation_extrapolation_amd.nets.vgg import my_vgg, vgg19_features
+    net, out = my_vgg(vgg19_features()), {}
+    for n, H, W in ((8, 256, 512), (1, 1024, 2048)):
+        g = E.Graph(torch.bfloat16)
+        net.lower_score(g, H, W)
+        _, arena, unaliased = E.arena_layout(g, 2 * n)
+        out[f"{n}x{H}x{W}"] = dict(arena_bytes=arena, unaliased_bytes=unaliased, arena_mib=arena / 2 ** 20,
+                                   unaliased_mib=unaliased / 2 ** 20, ratio=arena / unaliased)
+    return out
+
+
+def _vgg_op_times(scorer, pred, gt, reps=5):
+    """device time per launch of one scoring call (one chunk), from events around every op of the
+    plan run one by one: median over `reps` -> {"load", "conv", "pool", "cosfeat", "finalize"} in us
+    and the algorithmic GB/s of the load and cosine kernels"""
+    import ctypes
+    from deep_video_interpolation_extrapolation_amd import _lib as L
+    from deep_video_interpolation_extrapolation_amd import synth as S
+    n, H, W, _ = pred.shape
+    dev = pred.device
+    plan = scorer.net.score_plan(n, H, W, dev)
+    lut = scorer._table(dev)
+    ws = torch.empty((plan.cosfeat_ws_doubles,), dtype=torch.float64, device=dev)
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    plan.set_cosfeat(ws, out)
+    lib, stream = L.load(), L.stream_ptr(dev)
+    ops = plan.fwd_arr
+    names = {L.OP_CONV: "conv", L.OP_EW: "pool", L.OP_COSFEAT: "cosfeat"}
+    acc = {}
+    for _ in range(reps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(ops) - plan.fwd_off + 2)]
+        ev[0].record()
+        S.vgg_load(pred, gt, plan.input_view("vgg_in"), lut)
+        ev[1].record()
+        for i in range(plan.fwd_off, len(ops)):
+            L.check(lib.dvie_run_ops(ctypes.byref(ops[i]), 1, stream), "op")
+            ev[i - plan.fwd_off + 2].record()
+        torch.cuda.synchronize()
+        row = {"load": ev[0].elapsed_time(ev[1]) * 1e3}
+        for i in range(plan.fwd_off, len(ops)):
+            k = names[ops[i].kind] if i < len(ops) - 1 else "finalize"
+            row[k] = row.get(k, 0.0) + ev[i - plan.fwd_off + 1].elapsed_time(ev[i - plan.fwd_off + 2]) * 1e3
+        for k, v in row.items():
+            acc.setdefault(k, []).append(v)
+    us = {k: sorted(v)[len(v) // 2] for k, v in acc.items()}
+    es = 2 if scorer.net.dtype == torch.bfloat16 else 4
+    load_bytes = 2 * n * H * W * (3 + 8 * es)  # bytes read + the 8-channel pixel written
+    cos_bytes = sum(2 * n * (H >> k) * (W >> k) * c * es for k, c in enumerate((64, 128, 256, 512, 512)))
+    total = sum(us.values())
+    return dict(us=us, total_us=total, load_share=us["load"] / total, cosfeat_share=(us["cosfeat"] + us["finalize"]) / total,
+                load_gbs=load_bytes / us["load"] / 1e3, cosfeat_gbs=cos_bytes / us["cosfeat"] / 1e3)
+
+
+def vgg_numbers(dev, seconds):
+    """PerceptualScorer (a) against the per-frame (b) and full-batch (c) compositions of the public
+    ops, bf16; per-op times of a scoring call; one batch-8 forward for scale"""
+    from deep_video_interpolation_extrapolation_amd.synth import PerceptualScorer
+    os.environ["DVIE_PRECISION"] = "bf16"
+    scorer = PerceptualScorer(max_batch=8)
+    cosine = losses.VGGCosineLoss().to(dev)
+    out = {}
+    for n, H, W in ((8, 256, 512), (1, 1024, 2048)):
+        npix = n * H * W
+        sets = (320 << 20) // (6 * npix) + 1  # 6 B per pixel and set: more than the cache holds
+        pred, gt = ([torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(sets)]
+                    for _ in range(2))
+        k = [0]
+
+        def f32(x):
+            return x.permute(0, 3, 1, 2).float() / 255
+
+        def a_scorer():
+            i = k[0] = (k[0] + 1) % sets
+            scorer(pred[i], gt[i])
+
+        def b_per_frame():
+            i = k[0] = (k[0] + 1) % sets
+            for j in range(n):
+                cosine(f32(pred[i][j:j + 1]), f32(gt[i][j:j + 1]), False)
+
+        def c_full_batch():
+            i = k[0] = (k[0] + 1) % sets
+            cosine(f32(pred[i]), f32(gt[i]), False)
+
+        rates = _alternate(dict(a_scorer=a_scorer, b_per_frame=b_per_frame, c_full_batch=c_full_batch), seconds)
+        row = {name: dict(us=1e6 / sorted(v)[1], runs_us=[1e6 / r for r in v], min_us=1e6 / max(v), max_us=1e6 / min(v),
+                          spread=(max(v) - min(v)) / sorted(v)[1]) for name, v in rates.items()}
+        row["buffer_sets"] = sets
+        row["b_over_a"] = row["b_per_frame"]["us"] / row["a_scorer"]["us"]
+        row["c_over_a"] = row["c_full_batch"]["us"] / row["a_scorer"]["us"]
+        row["ops"] = _vgg_op_times(scorer, pred[0], gt[0])
+        out[f"{n}x{H}x{W}"] = row
+        del pred, gt
+        torch.cuda.empty_cache()
+    net = make_net().to(dev).eval()
+    frames = torch.randint(0, 256, (8, 2, 256, 512, 3), dtype=torch.uint8, device=dev)
+    labels = torch.randint(0, 20, (8, 2, 256, 512), dtype=torch.uint8, device=dev)
+    syn = VideoSynthesizer(net, max_batch=8)
+    fwd = lambda: syn.extrapolate(frames, labels, 1)  # noqa: E731
+    fwd()
+    fwd()
+    us = 1e6 / sorted(timed(fwd, seconds) for _ in range(3))[1]
+    out["forward_8x256x512_bf16_us"] = us
+    out["a_8x256x512_over_forward"] = out["8x256x512"]["a_scorer"]["us"] / us
+    return out
+
+
 def _alternate(legs, seconds, scale=1.0, rounds=3):
     """legs {name: fn}, warmed up, then timed alternating `rounds` times -> {name: calls/s * scale per
     round}"""
@@ -416,7 +535,17 @@ def main():
     ap.add_argument("--two-stage", action="store_true", help="only the two-stage legs")
     ap.add_argument("--score", action="store_true", help="only the held-out scoring legs")
     ap.add_argument("--pad", action="store_true", help="only the padded-canvas legs")
+    ap.add_argument("--vgg", action="store_true", help="only the perceptual-score legs")
     a = ap.parse_args()
+    if a.vgg:
+        res = dict(vgg_arena_bf16=vgg_arena_numbers())
+        if torch.cuda.is_available():
+            res["vgg_bf16"] = vgg_numbers(torch.device("cuda:0"), a.seconds)
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.pad:
         dev = torch.device("cuda:0")
         res = dict(pad_kernels=pad_kernel_numbers(dev, a.seconds),
