@@ -182,6 +182,14 @@ class SynthVggLoadDesc(ctypes.Structure):
     ]
 
 
+class SynthMsssimDesc(ctypes.Structure):
+    _fields_ = [
+        ("pred", vp), ("gt", vp), ("msssim", vp), ("parts", vp), ("ws", vp),
+        ("pred_s0", i64), ("pred_s1", i64), ("gt_s0", i64), ("gt_s1", i64),
+        ("n0", i32), ("n1", i32), ("h", i32), ("w", i32), ("scales", i32), ("pad0", i32),
+    ]
+
+
 class CosFeatDesc(ctypes.Structure):
     _fields_ = [
         ("feat", vp), ("ws", vp), ("out", vp), ("ld", i64),
@@ -297,6 +305,8 @@ _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, 
         OP_COSFEAT: CosFeatDesc, 100: WarpDesc, 101: SoftmaxDesc, 102: SnLayer, 103: ClipDesc,
         104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc, 107: SynthScoreDesc,
         108: SynthLoadPadDesc, 109: SynthFinishCropDesc, 110: SynthVggLoadDesc}
+# descriptors added after the set tests/test_perceptual_cpu.py pins for _ABI; load() checks both tables
+_ABI_MORE = {111: SynthMsssimDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -309,7 +319,7 @@ EXPORTS = [
     "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_pack_blocks", "dvie_trace_kernels", "dvie_traced_kernels",
     "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_score_ws_bytes",
     "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits", "dvie_bn_partial_doubles",
-    "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks",
+    "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks", "dvie_synth_msssim", "dvie_synth_msssim_ws_bytes",
 ]
 
 _lib = None
@@ -335,7 +345,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         lib.dvie_abi_sizeof.restype = ctypes.c_size_t
         lib.dvie_abi_sizeof.argtypes = [i32]
-        for which, st in _ABI.items():
+        for which, st in {**_ABI, **_ABI_MORE}.items():
             got = lib.dvie_abi_sizeof(which)
             if got != ctypes.sizeof(st):
                 raise DvieError(f"ABI mismatch for {st.__name__}: C {got} vs ctypes {ctypes.sizeof(st)}")
@@ -346,7 +356,7 @@ def load():
                      "dvie_head_bwd", "dvie_softmax_fwd", "dvie_softmax_bwd", "dvie_clip_prep", "dvie_attn",
                      "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
                      "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop",
-                     "dvie_synth_vgg_load", "dvie_cosfeat"):
+                     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_synth_msssim"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]
@@ -371,6 +381,8 @@ def load():
         lib.dvie_bn_partial_doubles.restype = ctypes.c_size_t
         lib.dvie_synth_score_ws_bytes.argtypes = [vp]
         lib.dvie_synth_score_ws_bytes.restype = ctypes.c_size_t
+        lib.dvie_synth_msssim_ws_bytes.argtypes = [vp]
+        lib.dvie_synth_msssim_ws_bytes.restype = ctypes.c_size_t
         lib.dvie_adamax.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]
         lib.dvie_scale.argtypes = [vp, i64, f32, vp]
         lib.dvie_adam.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]

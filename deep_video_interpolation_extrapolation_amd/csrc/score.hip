@@ -27,6 +27,7 @@
 // synth_score_finalize_kernel: one block per frame sums that frame's block partials, each
 // thread a fixed strided subset in order, then a fixed LDS tree -- the same bits every run.
 #include "common.h"
+#include "gauss11.h"
 
 namespace dvie {
 
@@ -38,17 +39,6 @@ constexpr int SC_SEG = 32;             // output rows of a segment
 constexpr int SC_HALO = 15;            // bytes of halo on each side (5 pixels)
 constexpr int SC_SPAN = SC_IT + 2 * SC_HALO;
 constexpr int SC_MAXC = 32;
-
-// exp(-(k - 5)^2 / (2 * 1.5^2)) / sum, in float64 (losses.py:18-20 under a float64 default)
-__host__ __device__ __forceinline__ constexpr double sc_g(int k) {
-  const int d = k < 5 ? 5 - k : k - 5;
-  return d == 0 ? 0.26601172486179436
-       : d == 1 ? 0.2130055377112537
-       : d == 2 ? 0.10936068950970002
-       : d == 3 ? 0.03600077212843083
-       : d == 4 ? 0.007598758135239185
-                : 0.00102838008447911;
-}
 
 struct sc_row {
   uint32_t a, b, ha, hb, lp, lg;  // centre byte of both frames, halo byte of both, the two labels

@@ -795,6 +795,7 @@ size_t dvie_abi_sizeof(int which) {
     case 108: return sizeof(dvie_synth_load_pad_desc);
     case 109: return sizeof(dvie_synth_finish_crop_desc);
     case 110: return sizeof(dvie_synth_vgg_load_desc);
+    case 111: return sizeof(dvie_synth_msssim_desc);
     default: return 0;
   }
 }

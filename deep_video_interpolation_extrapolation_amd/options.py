@@ -20,6 +20,9 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
                             `vgg` validation metric, synth.PerceptualScorer) -> "vgg" per clip and in the
                             summary of scores.json, and "vgg_weights"; taken on the top-left
                             (H // 16 * 16, W // 16 * 16) of the frames, which must be at least 16x16
+  --synth_msssim K          with --synth_eval: also the per-frame K-scale MS-SSIM (synth.frame_msssim,
+                            1 <= K <= 5; 0 = off) -> "msssim" per clip and in the summary of scores.json,
+                            and "msssim_scales"; a clip with min(H, W) >> (K - 1) < 11 ends the run
   --synth_pad {none,replicate}
                             --split test: `none` takes only clips whose height and width are multiples
                             of the net's coarsest stride (4; 8 with --highres_large; 4 << (--n_sc - 1)
@@ -82,6 +85,7 @@ GLOBAL = [
     ("--synth_levels", "synth_levels", int, 1, None),
     ("--synth_eval", "synth_eval", bool, False, None),
     ("--synth_vgg", "synth_vgg", bool, False, None),
+    ("--synth_msssim", "synth_msssim", int, 0, None),
     ("--synth_pad", "synth_pad", str, "none", ["none", "replicate"]),
 ]
 

@@ -168,16 +168,16 @@ class ExtraTrainer(InterTrainer):
         """--split test, extrapolation: --num_pred_step frames after the clip's last two"""
         return syn.extrapolate(frames[:, -2:], labels[:, -2:], steps=getattr(self.args, "num_pred_step", 1))
 
-    def _score(self, syn, frames, labels, clip, perceptual=None):
+    def _score(self, syn, frames, labels, clip, perceptual=None, msssim=None):
         """--split test --synth_eval, extrapolation: the clip's first two frames are the inputs,
         the next min(--num_pred_step, T - 2) the truth (None: the clip has no third frame);
-        perceptual: the PerceptualScorer of --synth_vgg"""
+        perceptual: the PerceptualScorer of --synth_vgg; msssim: the scales of --synth_msssim"""
         T = frames.shape[1]
         if T < 3:
             self.log.info(f"synth_eval: skip {clip}: {T} frames, 3 needed")
             return None
         n = 2 + min(getattr(self.args, "num_pred_step", 1), T - 2)
-        return syn.score_extrapolation(frames[:, :n], labels[:, :n], perceptual=perceptual)
+        return syn.score_extrapolation(frames[:, :n], labels[:, :n], perceptual=perceptual, msssim=msssim)
 
     def save_checkpoint(self):
         return super().save_checkpoint()

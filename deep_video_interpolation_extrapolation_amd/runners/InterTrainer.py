@@ -402,10 +402,10 @@ class InterTrainer:
                     Image.fromarray(np.ascontiguousarray(arr[k])).save(os.path.join(d, "{:04d}.png".format(k)))
         return root
 
-    def _score(self, syn, frames, labels, clip, perceptual=None):
+    def _score(self, syn, frames, labels, clip, perceptual=None, msssim=None):
         """--split test --synth_eval, interpolation: every 2**synth_levels-th frame is kept, the
         others are synthesised and scored (None: the clip is too short); perceptual: the
-        PerceptualScorer of --synth_vgg"""
+        PerceptualScorer of --synth_vgg; msssim: the scales of --synth_msssim"""
         step = 1 << getattr(self.args, "synth_levels", 1)
         T = frames.shape[1]
         keep = (T - 1) // step * step + 1
@@ -415,7 +415,7 @@ class InterTrainer:
         if keep < T:
             self.log.info(f"synth_eval: {clip}: the last {T - keep} of {T} frames dropped ((T - 1) % {step} != 0)")
         return syn.score_interpolation(frames[:, :keep], labels[:, :keep], levels=getattr(self.args, "synth_levels", 1),
-                                       perceptual=perceptual)
+                                       perceptual=perceptual, msssim=msssim)
 
     def test_eval(self):
         """--split test --synth_eval: the clips of test(), scored instead of written.  Per clip
@@ -426,14 +426,20 @@ class InterTrainer:
         goes to the log.  No PNG is written.  With --synth_vgg one synth.PerceptualScorer scores
         every clip too: "vgg" per clip, in the summary and in every per_position row, and a
         top-level "vgg_weights" naming the VGG19 weights (PerceptualScorer.weights_name); a clip
-        whose size is no multiple of 16 is scored on synth.vgg_region of it (logged once per clip)."""
+        whose size is no multiple of 16 is scored on synth.vgg_region of it (logged once per clip).
+        With --synth_msssim K every scored frame also gets its K-scale MS-SSIM (synth.frame_msssim):
+        "msssim" per clip, in the summary and in every per_position row, and a top-level
+        "msssim_scales"; a clip too small for K scales ends the run with a ValueError naming the
+        clip (K is never reduced: one scores.json holds one metric)."""
         import numpy as np
         from PIL import Image
-        from ..synth import PerceptualScorer, summarize, vgg_region
+        from ..synth import PerceptualScorer, msssim_check, summarize, vgg_region
         a = self.args
         syn = self._synthesizer()
         scorer = PerceptualScorer(max_batch=max(1, a.batch_size)) if getattr(a, "synth_vgg", False) else None
-        keys = ("psnr", "ssim", "acc", "miou") + (("vgg",) if scorer else ())
+        scales = getattr(a, "synth_msssim", 0) or None
+        extra = (("vgg",) if scorer else ()) + (("msssim",) if scales else ())
+        keys = ("psnr", "ssim", "acc", "miou") + extra
         img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
         clips, cols = {}, [[] for _ in range(1 + len(keys))]
         for clip in sorted(d for d in os.listdir(img_dir) if os.path.isdir(os.path.join(img_dir, d))):
@@ -446,17 +452,26 @@ class InterTrainer:
             if scorer and vgg_region(*imgs.shape[1:3]) != imgs.shape[1:3]:
                 self.log.info("synth_eval: {}: vgg is scored on the top-left {}x{} of the {}x{} frames".format(
                     clip, *vgg_region(*imgs.shape[1:3]), *imgs.shape[1:3]))
+            if scales:
+                try:
+                    msssim_check(*imgs.shape[1:3], scales)
+                except ValueError as e:
+                    raise ValueError(f"{clip}: {e}") from None
             sc = self._on_clip(self._score, syn, torch.from_numpy(imgs)[None].to(self.device),
-                               torch.from_numpy(labs)[None].to(self.device), clip, scorer)
+                               torch.from_numpy(labs)[None].to(self.device), clip, scorer, scales)
             if sc is None:
                 continue
-            vals = [v[0] for v in sc.host(vgg=scorer is not None)]  # psnr, ssim, acc, miou (, vgg) of the one clip
+            # psnr, ssim, acc, miou (, vgg) (, msssim) of the one clip
+            vals = [v[0] for v in sc.host(vgg=scorer is not None, msssim=scales is not None)]
             clips[clip] = dict(slots=sc.slots, **{k: v.tolist() for k, v in zip(keys, vals)})
             for col, v in zip(cols, [np.asarray(sc.positions)] + vals):
                 col.append(v)
-        res = dict(clips=clips, summary=summarize(*[np.concatenate(c) for c in cols]) if clips else None)
+        cat = [np.concatenate(c) for c in cols] if clips else None
+        res = dict(clips=clips, summary=summarize(*cat[:5], **dict(zip(extra, cat[5:]))) if clips else None)
         if scorer:
             res["vgg_weights"] = scorer.weights_name
+        if scales:
+            res["msssim_scales"] = scales
         root = os.path.join(a.cycgen_load_dir, "synth_eval")
         os.makedirs(root, exist_ok=True)
         with open(os.path.join(root, "scores.json"), "w") as f:

@@ -44,7 +44,8 @@ network's own output; the uint8 storage the caller gets stays (H, W).
 Scoring: `frame_scores` (PSNR, SSIM, label agreement: dvie_synth_score) and, opt-in,
 `PerceptualScorer`, the per-frame VGG19 feature cosine: `dvie_synth_vgg_load` fills the input
 buffer of my_vgg's forward-only, arena-allocated scoring plan from the uint8 frames, and the
-plan's own cosfeat ops reduce the five feature maps to one float64 per frame.
+plan's own cosfeat ops reduce the five feature maps to one float64 per frame; and
+`frame_msssim`, the per-frame multi-scale SSIM over an exact integer pyramid (dvie_synth_msssim).
 """
 import ctypes
 
@@ -178,12 +179,13 @@ class FrameScores:
     shaped like the leading dimensions of the frames -- sse (int64), ssim (float64) and, with
     label maps, agree, valid (int64), inter, uni (int64, a trailing class dimension); None
     without.  psnr / acc / miou are derived on the device in float64."""
-    FIELDS = ("sse", "ssim", "agree", "valid", "inter", "uni", "vgg")
+    FIELDS = ("sse", "ssim", "agree", "valid", "inter", "uni", "msssim", "vgg")
 
-    def __init__(self, H, W, sse, ssim, agree=None, valid=None, inter=None, uni=None, vgg=None):
+    def __init__(self, H, W, sse, ssim, agree=None, valid=None, inter=None, uni=None, vgg=None, msssim=None):
         self.H, self.W = H, W
         self.sse, self.ssim, self.agree, self.valid, self.inter, self.uni = sse, ssim, agree, valid, inter, uni
         self.vgg = vgg  # float64 VGG19 feature cosine per frame (frame_scores(..., perceptual=)), or None
+        self.msssim = msssim  # float64 multi-scale SSIM per frame (frame_scores(..., msssim=K)), or None
 
     @property
     def psnr(self):
@@ -210,7 +212,8 @@ class FrameScores:
 
     def map(self, fn):
         """the same scores with fn applied to every tensor (the class dimension stays last)"""
-        return FrameScores(self.H, self.W, *[None if getattr(self, k) is None else fn(getattr(self, k)) for k in self.FIELDS])
+        return FrameScores(self.H, self.W, **{k: None if getattr(self, k) is None else fn(getattr(self, k))
+                                              for k in self.FIELDS})
 
 
 def _lead_of(t, tail, what):
@@ -373,7 +376,64 @@ class PerceptualScorer:
         return out.reshape(lead)
 
 
-def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perceptual=None):
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)  # Wang, Simoncelli and Bovik (2003)
+
+
+def msssim_weights(K):
+    """the exponents of a K-scale MS-SSIM: the first K published weights divided by their sum"""
+    if not 1 <= K <= len(MSSSIM_WEIGHTS):
+        raise ValueError(f"msssim: scales={K} must be in 1..{len(MSSSIM_WEIGHTS)}")
+    total = sum(MSSSIM_WEIGHTS[:K])
+    return tuple(w / total for w in MSSSIM_WEIGHTS[:K])
+
+
+def msssim_max_scales(H, W):
+    """the largest K with min(H, W) >> (K - 1) >= 11, at most 5 (the coarsest level must hold a
+    whole 11-tap window); 0 for a side below 11.  Five scales need a shorter side of 176."""
+    K = 0
+    while K < len(MSSSIM_WEIGHTS) and (min(H, W) >> K) >= 11:
+        K += 1
+    return K
+
+
+def msssim_check(H, W, scales):
+    """ValueError unless (H, W) frames take `scales` MS-SSIM scales (the message names the largest
+    number that fits)"""
+    if not isinstance(scales, int) or isinstance(scales, bool) or not 1 <= scales <= len(MSSSIM_WEIGHTS):
+        raise ValueError(f"msssim: scales={scales!r} must be an int in 1..{len(MSSSIM_WEIGHTS)}")
+    fit = msssim_max_scales(H, W)
+    if scales > fit:
+        raise ValueError(f"msssim: {scales} scales need min(H, W) >> {scales - 1} >= 11; {H}x{W} frames take at most "
+                         f"{fit} scales")
+
+
+def frame_msssim(pred, gt, scales=5):
+    """Multi-scale SSIM of uint8 device frames `pred` (..., H, W, 3) against `gt` (what frame_scores
+    takes: up to two leading dimensions of any strides) -> (msssim, parts): float64 device tensors
+    shaped like the leading dimensions and like them + (scales,) (dvie_synth_msssim: a pyramid
+    launch, one level pass, a finalize launch; no host synchronisation).
+
+    Level s of the pyramid is (H >> s, W >> s): the mean of the 2**s x 2**s blocks of the frame,
+    trailing rows and columns dropped.  parts[..., s] is the mean of the contrast-structure map cs
+    of level s, for the last level of l * cs, with dvie_synth_score's window and border rule;
+    msssim = prod max(parts, 0) ** msssim_weights(scales).  scales=1 is frame_scores' ssim.
+    min(H, W) >> (scales - 1) must be at least 11 (ValueError naming msssim_max_scales(H, W))."""
+    lead, H, W, n0, n1, strides = _pairs_of(pred, gt)
+    msssim_check(H, W, scales)
+    dev = pred.device
+    d = L.SynthMsssimDesc()
+    d.pred, d.gt, d.n0, d.n1, d.h, d.w, d.scales = pred.data_ptr(), gt.data_ptr(), n0, n1, H, W, scales
+    d.pred_s0, d.pred_s1, d.gt_s0, d.gt_s1 = strides
+    out = torch.empty(lead, dtype=torch.float64, device=dev)
+    parts = torch.empty(lead + (scales,), dtype=torch.float64, device=dev)
+    lib = L.load()
+    ws = torch.empty((lib.dvie_synth_msssim_ws_bytes(ctypes.byref(d)),), dtype=torch.uint8, device=dev)
+    d.msssim, d.parts, d.ws = out.data_ptr(), parts.data_ptr(), ws.data_ptr()
+    L.check(lib.dvie_synth_msssim(ctypes.byref(d), L.stream_ptr(dev)), "synth msssim")
+    return out, parts
+
+
+def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perceptual=None, msssim=None):
     """Score uint8 device frames `pred` (..., H, W, 3) against `gt` and, when both are given,
     label maps `pred_labels` (..., H, W) against `gt_labels` (dvie_synth_score: one fused pass
     and a finalize launch, no host synchronisation) -> FrameScores shaped like the leading
@@ -381,7 +441,9 @@ def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perce
     extrapolate return are scored in place); the frame-level dimensions must be contiguous.
     perceptual: a PerceptualScorer -> the result also has `.vgg`, the per-frame VGG19 feature
     cosine on the region vgg_region(H, W) (up to 15 trailing rows and columns are not seen when
-    H or W is no multiple of 16; a side below 16 raises ValueError); None: `.vgg` is None."""
+    H or W is no multiple of 16; a side below 16 raises ValueError); None: `.vgg` is None.
+    msssim: an int K -> the result also has `.msssim`, frame_msssim(pred, gt, K)[0] (ValueError when
+    the frames are too small for K scales); None: `.msssim` is None."""
     L.require_gpu(pred)
     if pred.dim() < 3 or pred.shape[-1] != 3:
         raise ValueError(f"pred: uint8 (..., H, W, 3), got {tuple(pred.shape)}")
@@ -395,6 +457,8 @@ def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perce
         raise ValueError(f"n_classes={n_classes} must be in 1..32")
     if perceptual is not None:
         vgg_region(H, W)  # (a frame too small for the perceptual score fails before anything runs)
+    if msssim is not None:
+        msssim_check(H, W, msssim)
     d = L.SynthScoreDesc()
     d.n0, d.n1, d.pred_s0, d.pred_s1 = _lead_of(pred, (H, W, 3), "pred")
     for t, tail, what in ((gt, (H, W, 3), "gt"),) + (((pred_labels, (H, W), "pred_labels"),
@@ -420,21 +484,26 @@ def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perce
     L.check(lib.dvie_synth_score(ctypes.byref(d), L.stream_ptr(dev)), "synth score")
     if perceptual is not None:
         out.vgg = perceptual(pred, gt)
+    if msssim is not None:
+        out.msssim = frame_msssim(pred, gt, msssim)[0]
     return out
 
 
-def summarize(position, psnr, ssim, acc, miou, vgg=None):
+def summarize(position, psnr, ssim, acc, miou, vgg=None, msssim=None):
     """Host-side means of per-frame scores (numpy arrays of one length; `position` an integer
     per frame) -> {"psnr", "ssim", "acc", "miou", "frames", "per_position": {position: the same
     four and "frames"}} as Python floats.  The mean PSNR is the mean of the per-frame PSNRs
     (losses.py:103-116); an infinite value stays infinite.  With `vgg` (the per-frame perceptual
-    scores) the result and every per_position row also have "vgg"."""
+    scores) the result and every per_position row also have "vgg", with `msssim` (the per-frame
+    multi-scale SSIM) "msssim"."""
     import numpy as np
     position = np.asarray(position)
     cols = dict(psnr=np.asarray(psnr, dtype=np.float64), ssim=np.asarray(ssim, dtype=np.float64),
                 acc=np.asarray(acc, dtype=np.float64), miou=np.asarray(miou, dtype=np.float64))
     if vgg is not None:
         cols["vgg"] = np.asarray(vgg, dtype=np.float64)
+    if msssim is not None:
+        cols["msssim"] = np.asarray(msssim, dtype=np.float64)
 
     def means(sel):
         with np.errstate(invalid="ignore"):
@@ -451,8 +520,8 @@ class SynthScores:
     """What score_interpolation / score_extrapolation return: `slots`, the scored time indices
     (interpolation: indices into the clip; extrapolation: the step index k of original frame
     2 + k); `scores`, the FrameScores of shape (B, len(slots)), whose tensors and derived
-    values are also attributes here (sse, ssim, agree, valid, inter, uni, psnr, acc, miou, and
-    vgg when a PerceptualScorer was passed);
+    values are also attributes here (sse, ssim, agree, valid, inter, uni, psnr, acc, miou, vgg
+    when a PerceptualScorer was passed and msssim when a number of scales was);
     `frames` / `labels`, the synthesised video as interpolate / extrapolate returns it;
     `positions`, per slot the position the summary groups by (slot % 2**levels, or the step)."""
 
@@ -464,21 +533,28 @@ class SynthScores:
             return getattr(self.scores, name)
         raise AttributeError(name)
 
-    def host(self, vgg=False):
-        """psnr, ssim, acc, miou -- with vgg=True also vgg (scored with a PerceptualScorer) -- as
-        float64 numpy arrays (B, len(slots)): one copy to the host"""
+    def host(self, vgg=False, msssim=False):
+        """psnr, ssim, acc, miou -- with vgg=True also vgg (scored with a PerceptualScorer), with
+        msssim=True also msssim (scored with msssim=K), after the others -- as float64 numpy
+        arrays (B, len(slots)): one copy to the host"""
         s = self.scores
         if vgg and s.vgg is None:
             raise ValueError("these scores have no vgg column (score_* was called without perceptual=)")
-        return tuple(torch.stack([s.psnr, s.ssim, s.acc, s.miou] + ([s.vgg] if vgg else [])).cpu().numpy())
+        if msssim and s.msssim is None:
+            raise ValueError("these scores have no msssim column (score_* was called without msssim=)")
+        return tuple(torch.stack([s.psnr, s.ssim, s.acc, s.miou] + ([s.vgg] if vgg else [])
+                                 + ([s.msssim] if msssim else [])).cpu().numpy())
 
     def summary(self):
         """Means over all scored frames and per position (summarize) as Python floats -- the
-        one place that copies to the host.  "vgg" is included when the scores have it."""
+        one place that copies to the host.  "vgg" and "msssim" are included when the scores have
+        them."""
         import numpy as np
-        cols = self.host(vgg=self.scores.vgg is not None)
+        extra = [k for k in ("vgg", "msssim") if getattr(self.scores, k) is not None]
+        cols = self.host(**{k: True for k in extra})
         pos = np.broadcast_to(np.asarray(self.positions), cols[0].shape)
-        return summarize(pos.ravel(), *[c.ravel() for c in cols])
+        return summarize(pos.ravel(), *[c.ravel() for c in cols[:4]],
+                         **{k: c.ravel() for k, c in zip(extra, cols[4:])})
 
 
 class FrameSizeError(ValueError):
@@ -777,43 +853,50 @@ class VideoSynthesizer:
         return fr[2:].transpose(0, 1), lb[2:].transpose(0, 1)
 
     # ---------------- held-out scoring ----------------
-    def score_interpolation(self, frames, labels, levels=1, perceptual=None):
+    def score_interpolation(self, frames, labels, levels=1, perceptual=None, msssim=None):
         """Held-out scoring of interpolation: frames (B, T, H, W, 3) and labels (B, T, H, W) of
         real clips with (T - 1) % 2**levels == 0 and T > 2**levels.  Frames 0, 2**levels, ...
         go through interpolate(..., levels); every other slot t is scored against original
         frame and label map t (heldout_slots) -> SynthScores, tensors (B, len(slots)).  The
         slots at one offset inside the period are one strided (B, G) view of the synthesised
         and of the original video, scored in place: 2**levels - 1 scoring calls.
-        perceptual: a PerceptualScorer -> the scores also have `.vgg` (frame_scores)."""
+        perceptual: a PerceptualScorer -> the scores also have `.vgg` (frame_scores); msssim: a
+        number of scales K -> they also have `.msssim`."""
         self._check(frames, labels)
         if perceptual is not None:
             vgg_region(*frames.shape[2:4])  # (too small a frame fails before the synthesis runs)
+        if msssim is not None:
+            msssim_check(*frames.shape[2:4], msssim)
         T, step = frames.shape[1], 1 << max(levels, 0)
         slots = heldout_slots(T, levels)
         out_f, out_l = self.interpolate(frames[:, ::step], labels[:, ::step], levels)
         parts = [frame_scores(out_f[:, o::step], frames[:, o::step], out_l[:, o::step], labels[:, o::step],
-                              n_classes=self.cm.n_classes, perceptual=perceptual) for o in range(1, step)]
+                              n_classes=self.cm.n_classes, perceptual=perceptual, msssim=msssim)
+                 for o in range(1, step)]
         # (B, G) per offset -> (B, G, step - 1) -> (B, G * (step - 1)): ascending slots
         scores = parts[0].map(lambda _: None)
         for k in FrameScores.FIELDS:
-            if getattr(parts[0], k) is None:  # (vgg without a scorer)
+            if getattr(parts[0], k) is None:  # (vgg without a scorer, msssim without scales)
                 continue
             t = torch.stack([getattr(p, k) for p in parts], dim=2)
             setattr(scores, k, t.reshape((t.shape[0], len(slots)) + tuple(t.shape[3:])))
         return SynthScores(slots, [t % step for t in slots], scores, out_f, out_l)
 
-    def score_extrapolation(self, frames, labels, perceptual=None):
+    def score_extrapolation(self, frames, labels, perceptual=None, msssim=None):
         """Held-out scoring of extrapolation: frames (B, 2 + S, H, W, 3), S >= 1.  The first two
         frames are the inputs of extrapolate(..., steps=S); step k is scored against original
         frame 2 + k -> SynthScores with slots 0 .. S-1, tensors (B, S).
-        perceptual: a PerceptualScorer -> the scores also have `.vgg` (frame_scores)."""
+        perceptual: a PerceptualScorer -> the scores also have `.vgg` (frame_scores); msssim: a
+        number of scales K -> they also have `.msssim`."""
         self._check(frames, labels)
         if perceptual is not None:
             vgg_region(*frames.shape[2:4])
+        if msssim is not None:
+            msssim_check(*frames.shape[2:4], msssim)
         S = frames.shape[1] - 2
         if S < 1:
             raise ValueError("score_extrapolation needs two input frames and at least one frame of truth")
         out_f, out_l = self.extrapolate(frames[:, :2], labels[:, :2], steps=S)
         scores = frame_scores(out_f, frames[:, 2:], out_l, labels[:, 2:], n_classes=self.cm.n_classes,
-                              perceptual=perceptual)
+                              perceptual=perceptual, msssim=msssim)
         return SynthScores(range(S), range(S), scores, out_f, out_l)

@@ -1038,11 +1038,53 @@ typedef struct dvie_synth_vgg_load_desc {
 
 int dvie_synth_vgg_load(const dvie_synth_vgg_load_desc* d, void* stream);
 
+/*
+ * dvie_synth_msssim: per-frame multi-scale SSIM (Wang, Simoncelli and Bovik, 2003) of uint8 frames
+ * against the originals (synth.frame_msssim).  Frames are addressed as dvie_synth_score addresses
+ * them: N = n0 * n1 pairs, frame (i0, i1) at base + i0*s0 + i1*s1 BYTES, a frame a contiguous
+ * h*w*3 block of uint8 RGB, no alignment assumed.  K = scales, 1 <= K <= 5.
+ *
+ * Pyramid: level s (0 <= s < K) has size (h >> s, w >> s); its pixel (i, j, c) is the mean of the
+ *   2^s x 2^s block of level 0 whose top-left is (i << s, j << s).  Trailing rows and columns that
+ *   do not fill a block are dropped (s applications of a 2x2 average pooling, in exact
+ *   arithmetic).  A level is held as the uint16 block SUM (<= 255 * 4^4 = 65280), exactly.
+ * Per level: the window and border rule of dvie_synth_score -- 11-tap gaussian, sigma 1.5,
+ *   normalised in float64, separable, samples outside the level's image 0, all arithmetic
+ *   float64 -- on the sums, with C1 = (0.01 * 255 * 4^s)^2, C2 = (0.03 * 255 * 4^s)^2 (a power-of-
+ *   two scaling of working on the means: the same bits):
+ *     cs = (2*s12 + C2) / (s1 + s2 + C2)        l = (2*mu1*mu2 + C1) / (mu1^2 + mu2^2 + C1)
+ *   parts[f][s] = mean over the level's pixels and the 3 channels of cs (s < K-1), of l * cs
+ *   (s = K-1).
+ * msssim[f] = prod_s max(parts[f][s], 0) ^ w_s, w the first K of (0.0448, 0.2856, 0.3001, 0.2363,
+ *   0.1333) divided by their sum (float64 pow).  With K = 1 this is dvie_synth_score's ssim.
+ * Size rule: min(h, w) >> (K - 1) >= 11 (the coarsest level holds a whole window).
+ *
+ * Launches: a pyramid launch (K >= 2; integer arithmetic only, both frames' bytes read once, levels
+ * 1 .. K-1 written to ws), one level-pass launch whose grid covers all K levels, a finalize launch.
+ * Bitwise reproducible: float64 block partials in ws, summed in a fixed order; no float atomics;
+ * no host synchronisation.
+ * ws: dvie_synth_msssim_ws_bytes(d) bytes (0 for a descriptor whose sizes are invalid), 8-byte
+ * aligned.  msssim (N float64) and parts (N x scales float64) 8-byte aligned, written by the call.
+ * n0, n1 >= 1, n0 * n1 <= 65535, h, w <= 2^19.
+ */
+typedef struct dvie_synth_msssim_desc {
+  const uint8_t* pred;
+  const uint8_t* gt;
+  double* msssim;
+  double* parts;
+  void* ws;
+  long long pred_s0, pred_s1, gt_s0, gt_s1; /* byte strides of (i0, i1) */
+  int n0, n1, h, w, scales, pad0;
+} dvie_synth_msssim_desc;
+
+size_t dvie_synth_msssim_ws_bytes(const dvie_synth_msssim_desc* d);
+int dvie_synth_msssim(const dvie_synth_msssim_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
- * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load). */
+ * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

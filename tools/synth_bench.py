@@ -36,7 +36,14 @@
   algorithmic GB/s of the load and cosine kernels; arena against one buffer per activation; and
   one batch-8 forward for scale.
 
-    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json] [--two-stage | --score | --pad | --vgg]
+* multi-scale SSIM (--msssim): us per call of synth.frame_msssim at 5 scales and at 1 beside
+  synth.frame_scores on the same frames (no label maps: the SSIM / squared-error pass), 8 pairs at
+  256x512 and 1 pair at 1024x2048, rotating over buffer sets that exceed the Infinity Cache, the
+  legs alternating, three rounds, the median, with the ratio to frame_scores (the pyramid holds
+  1.33 times the pixels of level 0).
+
+    python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json]
+                                [--two-stage | --score | --pad | --vgg | --msssim]
 """
 import argparse
 import json
@@ -53,8 +60,8 @@ from deep_video_interpolation_extrapolation_amd import nets  # noqa: E402
 from deep_video_interpolation_extrapolation_amd.runners.InterTrainer import InterTrainer  # noqa: E402
 from deep_video_interpolation_extrapolation_amd import losses  # noqa: E402
 from deep_video_interpolation_extrapolation_amd.synth import (VideoSynthesizer, frame_scores, synth_bridge,  # noqa: E402
-                                                              synth_finish, synth_finish_crop, synth_load,
-                                                              synth_load_pad)
+                                                              frame_msssim, synth_finish, synth_finish_crop,
+                                                              synth_load, synth_load_pad)
 
 
 def make_net(large=False):
@@ -361,6 +368,38 @@ def _alternate(legs, seconds, scale=1.0, rounds=3):
     return rates
 
 
+def msssim_numbers(dev, seconds):
+    """frame_msssim at 5 scales and at 1 beside frame_scores (no label maps), alternating, three
+    rounds"""
+    out = {}
+    for n, H, W in ((8, 256, 512), (1, 1024, 2048)):
+        npix = n * H * W
+        sets = (320 << 20) // (6 * npix) + 1  # 6 B per pixel and set: more than the cache holds
+        pred, gt = ([torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(sets)]
+                    for _ in range(2))
+        k = [0]
+
+        def rot(fn):
+            def run():
+                i = k[0] = (k[0] + 1) % sets
+                fn(pred[i], gt[i])
+            return run
+
+        legs = dict(score=rot(frame_scores), msssim_k5=rot(lambda a, b: frame_msssim(a, b, 5)),
+                    msssim_k1=rot(lambda a, b: frame_msssim(a, b, 1)))
+        rates = _alternate(legs, seconds)
+        row = {name: dict(us=1e6 / sorted(v)[1], runs_us=[1e6 / r for r in v], spread=(max(v) - min(v)) / sorted(v)[1])
+               for name, v in rates.items()}
+        row["buffer_sets"] = sets
+        for name in legs:
+            if name != "score":
+                row[f"{name}_over_score"] = row[name]["us"] / row["score"]["us"]
+        out[f"{n}x{H}x{W}"] = row
+        del pred, gt
+        torch.cuda.empty_cache()
+    return out
+
+
 def pad_kernel_numbers(dev, seconds):
     """load_pad / finish_crop against load / finish on the same canvas, rotating over buffer sets of
     more than 2 GB in all (every launch streams from HBM).  GB/s are of algorithmic bytes: finish
@@ -536,7 +575,15 @@ def main():
     ap.add_argument("--score", action="store_true", help="only the held-out scoring legs")
     ap.add_argument("--pad", action="store_true", help="only the padded-canvas legs")
     ap.add_argument("--vgg", action="store_true", help="only the perceptual-score legs")
+    ap.add_argument("--msssim", action="store_true", help="only the multi-scale SSIM legs")
     a = ap.parse_args()
+    if a.msssim:
+        res = dict(msssim=msssim_numbers(torch.device("cuda:0"), a.seconds))
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.vgg:
         res = dict(vgg_arena_bf16=vgg_arena_numbers())
         if torch.cuda.is_available():
