@@ -25,6 +25,7 @@ OP_SEGENC_BWD = 15
 OP_WREDUCE_MULTI = 16
 OP_COSFEAT = 17
 COSFEAT_MAX_TAPS = 8
+YUV_420, YUV_444 = 420, 444
 (ATTN_L2NORM, ATTN_L2NORM_BWD, ATTN_CORR, ATTN_GATHER, ATTN_GATHER_T, ATTN_SOFTMAX, ATTN_SOFTMAX_BWD, ATTN_WNORM,
  ATTN_WNORM_BWD, ATTN_POOL, ATTN_POOL_T) = range(11)
 
@@ -190,6 +191,14 @@ class SynthMsssimDesc(ctypes.Structure):
     ]
 
 
+class SynthYuvDesc(ctypes.Structure):
+    _fields_ = [
+        ("yuv", vp), ("rgb", vp), ("yuv_stride", i64), ("rgb_stride", i64), ("rgb_row_stride", i64),
+        ("n", i32), ("h", i32), ("w", i32), ("layout", i32), ("yo", i32), ("pad0", i32),
+        ("table", i32 * 12),
+    ]
+
+
 class CosFeatDesc(ctypes.Structure):
     _fields_ = [
         ("feat", vp), ("ws", vp), ("out", vp), ("ld", i64),
@@ -306,7 +315,7 @@ _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, 
         104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc, 107: SynthScoreDesc,
         108: SynthLoadPadDesc, 109: SynthFinishCropDesc, 110: SynthVggLoadDesc}
 # descriptors added after the set tests/test_perceptual_cpu.py pins for _ABI; load() checks both tables
-_ABI_MORE = {111: SynthMsssimDesc}
+_ABI_MORE = {111: SynthMsssimDesc, 112: SynthYuvDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -320,6 +329,7 @@ EXPORTS = [
     "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_score_ws_bytes",
     "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits", "dvie_bn_partial_doubles",
     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks", "dvie_synth_msssim", "dvie_synth_msssim_ws_bytes",
+    "dvie_synth_yuv2rgb", "dvie_synth_rgb2yuv",
 ]
 
 _lib = None
@@ -356,7 +366,8 @@ def load():
                      "dvie_head_bwd", "dvie_softmax_fwd", "dvie_softmax_bwd", "dvie_clip_prep", "dvie_attn",
                      "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
                      "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop",
-                     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_synth_msssim"):
+                     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_synth_msssim", "dvie_synth_yuv2rgb",
+                     "dvie_synth_rgb2yuv"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]

@@ -796,6 +796,7 @@ size_t dvie_abi_sizeof(int which) {
     case 109: return sizeof(dvie_synth_finish_crop_desc);
     case 110: return sizeof(dvie_synth_vgg_load_desc);
     case 111: return sizeof(dvie_synth_msssim_desc);
+    case 112: return sizeof(dvie_synth_yuv_desc);
     default: return 0;
   }
 }

@@ -5,7 +5,7 @@
 
 Same flags (options.py) and the same trainer dispatch as the reference worker()
 (main.py:85-119): EXTRA -> ExtraTrainer, INTER --gan -> InterGANTrainer, INTER ->
-InterTrainer; then validate / cycgen / test (synth.VideoSynthesizer over PNG clips) / the
+InterTrainer; then validate / cycgen / test (synth.VideoSynthesizer over PNG or Y4M clips) / the
 epoch loop with rank-0 checkpoints.  Instead of
 mp.spawn + a tcp:// rendezvous (main.py:133-154), one process per GPU comes from torchrun
 (RANK / LOCAL_RANK / WORLD_SIZE), and torch.distributed's 'nccl' backend is RCCL over xGMI.
@@ -94,7 +94,7 @@ def main(argv=None):
     elif args.split == "cycgen":  # reference main.py:108-110
         assert args.cycgen_load_dir is not None, "please specify cycgen load dir where to load data"
         trainer.cycgen()
-    elif args.split == "test":  # device-resident synthesis of the PNG clips under --cycgen_load_dir
+    elif args.split == "test":  # device-resident synthesis of the PNG / Y4M clips under --cycgen_load_dir
         assert args.cycgen_load_dir is not None, "please specify --cycgen_load_dir (clips under rgb/ and seg/)"
         trainer.test()
     else:  # 'mycycgen'

@@ -29,10 +29,33 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
                             for the refinement stages); `replicate` takes any size: the clip is
                             synthesised on a canvas rounded up to that multiple, its last row and
                             column repeated, and the PNGs and scores have the clip's own size
+  --synth_window N          --split test, INTER: N >= 2 runs every clip in windows of N input frames that
+                            share their boundary frame (synth.window_plan, interpolate_stream): the clip
+                            is read, synthesised and written window by window, one thread reading the
+                            next window and one writing the previous while the device works, so device
+                            and host memory depend on N and not on the clip's length.  0 (default): the
+                            whole clip at once.  1 or a negative value is an error.  EXTRA ignores it
+                            (it reads a clip's last two frames; --num_pred_step bounds its memory)
+  --synth_yuv {bt601,bt709} --split test: the matrix of the Y'CbCr <-> RGB conversion of .y4m clips.  A
+                            clip is a directory of PNGs under <cycgen_load_dir>/rgb (labels: the same
+                            names under seg) or a file rgb/<name>.y4m with its labels in seg/<name>.y4m
+                            (YUV4MPEG2: C420*, C444 or Cmono, 8 bit; the labels' Y plane is the class
+                            id); a .y4m clip is written as synth/{rgb,seg,vis_seg}/<name>.y4m.  Y4M has
+                            no tag for the matrix: bt601 (default) is what swscale writes and assumes
+                            for an untagged stream; the range follows the file's XCOLORRANGE tag
 """
 import argparse
 
 _ADAMAX = ["adamax", "adam", "sgd"]
+
+
+def _window(text):
+    """--synth_window: 0 (off) or a window of at least two input frames"""
+    n = int(text)
+    if n == 1 or n < 0:
+        raise argparse.ArgumentTypeError(f"--synth_window {n}: a window holds at least 2 input frames (0 = the whole clip)")
+    return n
+
 
 # (flag, dest, kind, default, choices)  kind: str/int/float/bool(store_true)
 GLOBAL = [
@@ -87,6 +110,8 @@ GLOBAL = [
     ("--synth_vgg", "synth_vgg", bool, False, None),
     ("--synth_msssim", "synth_msssim", int, 0, None),
     ("--synth_pad", "synth_pad", str, "none", ["none", "replicate"]),
+    ("--synth_window", "synth_window", _window, 0, None),
+    ("--synth_yuv", "synth_yuv", str, "bt601", ["bt601", "bt709"]),
 ]
 
 # second-stage flags of the reference's INTER sub-command (options/options.py:296-380);

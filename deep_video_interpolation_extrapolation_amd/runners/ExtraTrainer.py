@@ -164,6 +164,8 @@ class ExtraTrainer(InterTrainer):
             self._scalars("val/score", res)
         return res
 
+    _streams = False  # extrapolation reads a clip's last two frames: --synth_window does not apply
+
     def _synthesize(self, syn, frames, labels):
         """--split test, extrapolation: --num_pred_step frames after the clip's last two"""
         return syn.extrapolate(frames[:, -2:], labels[:, -2:], steps=getattr(self.args, "num_pred_step", 1))

@@ -368,15 +368,21 @@ class InterTrainer:
         """--split test, interpolation: --synth_levels frame-rate doublings of the whole clip"""
         return syn.interpolate(frames, labels, levels=getattr(self.args, "synth_levels", 1))
 
+    _streams = True  # --synth_window applies: interpolation runs in windows (ExtraTrainer: False)
+
     def test(self):
-        """--split test: for each clip directory under --cycgen_load_dir/rgb (and /seg, the same
-        file names), all PNGs in sorted order -> synth.VideoSynthesizer on the device (INTER:
-        interpolate with --synth_levels; EXTRA: extrapolate --num_pred_step frames from the
-        last two) -> <cycgen_load_dir>/synth/{rgb,seg,vis_seg}/<clip>/NNNN.png: the frames, the
-        label maps and their palette colouring, numbered in output order."""
+        """--split test: for each clip under --cycgen_load_dir/rgb -> synth.VideoSynthesizer on the
+        device (INTER: interpolate with --synth_levels; EXTRA: extrapolate --num_pred_step frames
+        from the last two).  A clip is a directory of PNGs (labels: the same file names under /seg),
+        all PNGs in sorted order -> <cycgen_load_dir>/synth/{rgb,seg,vis_seg}/<clip>/NNNN.png: the
+        frames, the label maps and their palette colouring, numbered in output order; or a file
+        <clip>.y4m (labels: /seg/<clip>.y4m, the Y plane the class id) ->
+        synth/{rgb,seg,vis_seg}/<clip>.y4m (_stream_clip, _whole_y4m).  INTER with --synth_window N
+        >= 2 runs every clip in windows of N input frames with overlapped I/O (_stream_clip)."""
         import numpy as np
         from PIL import Image
         from ..utils.net_utils import CITYSCAPES_COLORS
+        from ..video_io import PngClip, Y4MClip
         a = self.args
         assert self.rank == 0, "test runs on one worker"
         assert a.cycgen_load_dir is not None, "please specify --cycgen_load_dir"
@@ -386,7 +392,11 @@ class InterTrainer:
         img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
         root = os.path.join(a.cycgen_load_dir, "synth")
         palette = np.array(CITYSCAPES_COLORS, dtype=np.uint8)
+        window = getattr(a, "synth_window", 0) if self._streams else 0
         for clip in sorted(d for d in os.listdir(img_dir) if os.path.isdir(os.path.join(img_dir, d))):
+            if window >= 2:
+                self._stream_clip(syn, PngClip(img_dir, seg_dir, clip), window, root, palette)
+                continue
             names = sorted(f for f in os.listdir(os.path.join(img_dir, clip)) if f.lower().endswith(".png"))
             assert len(names) >= 2, f"{clip}: a clip needs at least two frames"
             imgs = np.stack([np.asarray(Image.open(os.path.join(img_dir, clip, f)).convert("RGB")) for f in names])
@@ -400,7 +410,117 @@ class InterTrainer:
                 os.makedirs(d, exist_ok=True)
                 for k in range(arr.shape[0]):
                     Image.fromarray(np.ascontiguousarray(arr[k])).save(os.path.join(d, "{:04d}.png".format(k)))
+        for fname in self._y4m_clips(img_dir):
+            src = Y4MClip(img_dir, seg_dir, fname)
+            try:
+                if self._streams:
+                    self._stream_clip(syn, src, window, root, palette)
+                else:
+                    self._whole_y4m(syn, src, root, palette)
+            finally:
+                src.close()
         return root
+
+    @staticmethod
+    def _y4m_clips(img_dir):
+        """the .y4m clip files of a clip directory, sorted"""
+        return sorted(f for f in os.listdir(img_dir) if f.lower().endswith(".y4m") and os.path.isfile(os.path.join(img_dir, f)))
+
+    def _upload(self, src, host, originals=None):
+        """one chunk of a clip as its reader thread left it -> (frames (1, t, H, W, 3), labels
+        (1, t, H, W)) on the device.  PNG: the decoded arrays; Y4M: the packed frames, converted by
+        synth.yuv_to_rgb (--synth_yuv, the file's range), and the Y plane of the packed labels;
+        `originals` (a deque) gets the packed device frame of every input frame, in order."""
+        from ..synth import yuv_to_rgb
+        a, b = (torch.from_numpy(x).to(self.device) for x in host)
+        if src.kind == "png":
+            return a[None], b[None]
+        H, W = src.height, src.width
+        frames = yuv_to_rgb(a, H, W, src.rgb.colourspace, getattr(self.args, "synth_yuv", "bt601"), src.rgb.full_range)
+        if originals is not None:
+            originals.extend(a.unbind(0))
+        return frames[None], b[:, :H * W].reshape(-1, H, W).contiguous()[None]
+
+    def _pack_y4m(self, src, out_f, out_l, palette, originals=None, first=0, step=0):
+        """frames (S, H, W, 3) and labels (S, H, W) of one Y4M clip on the device (any stride over S)
+        -> what Y4MSink.write takes, on the host: the packed frames in the input's colourspace, the
+        label maps, and their palette colouring packed as C444.  step >= 1: slots first, first +
+        step, ... are input frames and get their own packed bytes, copied from the deque
+        `originals`; only the other slots go through synth.rgb_to_yuv, each residue modulo step
+        as one strided run read and written in place.  step 0: every slot is converted."""
+        from ..synth import rgb_to_yuv
+        from ..video_io import frame_bytes
+        S, H, W = out_l.shape
+        cs, full, matrix = src.rgb.colourspace, src.rgb.full_range, getattr(self.args, "synth_yuv", "bt601")
+        pk = torch.empty((S, frame_bytes(W, H, cs)), dtype=torch.uint8, device=out_f.device)
+        if step:
+            for i in range(first, S, step):
+                pk[i].copy_(originals.popleft())
+        for r in ([0] if not step else [r for r in range(min(step, S)) if r != first]):
+            rgb_to_yuv(out_f[r::max(step, 1)], cs, matrix, full, out=pk[r::max(step, 1)])
+        vis = palette[out_l.clamp(max=palette.shape[0] - 1).long()]  # (ids past the classes: "none")
+        vis = rgb_to_yuv(vis, "C444", matrix, full)
+        return pk.cpu().numpy(), out_l.reshape(S, H * W).cpu().numpy(), vis.cpu().numpy()
+
+    def _stream_clip(self, syn, src, window, root, palette):
+        """--split test, interpolation, one clip in windows (window 0: a .y4m clip as one window):
+        a reader thread prepares the next window (file reads, PNG decoding), this thread copies it
+        to the device, runs VideoSynthesizer.interpolate_stream and copies the result back, a
+        writer thread encodes and writes it; both queues hold at most two windows.  Every HIP call
+        is made here.  Output slots are numbered across windows; for a .y4m clip the slots at the
+        multiples of 2**synth_levels are the input's packed bytes, written back untouched."""
+        import collections
+        import time
+        from ..synth import FrameSizeError
+        from ..video_io import BackgroundWriter, PngSink, Prefetcher, Y4MSink
+        levels = getattr(self.args, "synth_levels", 1)
+        step = 1 << levels
+        if src.kind == "png":
+            sink = PngSink(root, src.name, palette)
+        else:
+            num, den = src.rgb.fps
+            sink = Y4MSink(root, src.name, src.width, src.height, (num * step, den), src.rgb.colourspace,
+                           src.rgb.full_range)
+            palette = torch.from_numpy(palette).to(self.device)
+        originals = collections.deque()
+        t_start, g0 = time.perf_counter(), 0
+        try:
+            with Prefetcher(src.chunks(window)) as reader, BackgroundWriter(sink.write) as writer:
+                on_device = (self._upload(src, host, originals if src.kind == "y4m" else None) for host in reader)
+                try:
+                    for out_f, out_l in syn.interpolate_stream(on_device, levels=levels):
+                        S = out_f.shape[1]
+                        if src.kind == "png":
+                            writer.put((g0, out_f[0].cpu().numpy(), out_l[0].cpu().numpy()))
+                        else:
+                            writer.put(self._pack_y4m(src, out_f[0], out_l[0], palette, originals, (-g0) % step, step))
+                        g0 += S
+                        del out_f, out_l
+                except FrameSizeError as e:
+                    raise FrameSizeError(f"{e} (--synth_pad replicate takes clips of any size)") from None
+                torch.cuda.synchronize(self.device)
+                t_dev = time.perf_counter()
+        finally:
+            sink.close()
+        t_end = time.perf_counter()
+        self.log.info("synth: {}: {} slots in {:.3f} s ({:.1f} slots/s); reader busy {:.3f} s, this thread waited for it "
+                      "{:.3f} s and for the writer {:.3f} s, writer busy {:.3f} s ({:.3f} s after the last window)".format(
+                          src.name, g0, t_end - t_start, g0 / max(t_end - t_start, 1e-9), reader.busy, reader.waited,
+                          writer.waited, writer.busy, t_end - t_dev))
+
+    def _whole_y4m(self, syn, src, root, palette):
+        """--split test, extrapolation, one .y4m clip: read whole, --num_pred_step frames predicted from
+        its last two, every one of them written through synth.rgb_to_yuv at the input's frame rate"""
+        from ..video_io import Y4MSink
+        host = list(src.chunks(0))
+        if not host or host[0][0].shape[0] < 2:
+            raise ValueError(f"{src.name}: a clip needs at least two frames")
+        frames, labels = self._on_clip(self._synthesize, syn, *self._upload(src, host[0]))
+        sink = Y4MSink(root, src.name, src.width, src.height, src.rgb.fps, src.rgb.colourspace, src.rgb.full_range)
+        try:
+            sink.write(self._pack_y4m(src, frames[0], labels[0], torch.from_numpy(palette).to(self.device)))
+        finally:
+            sink.close()
 
     def _score(self, syn, frames, labels, clip, perceptual=None, msssim=None):
         """--split test --synth_eval, interpolation: every 2**synth_levels-th frame is kept, the
@@ -466,6 +586,8 @@ class InterTrainer:
             clips[clip] = dict(slots=sc.slots, **{k: v.tolist() for k, v in zip(keys, vals)})
             for col, v in zip(cols, [np.asarray(sc.positions)] + vals):
                 col.append(v)
+        for fname in self._y4m_clips(img_dir):
+            self.log.info(f"synth_eval: skip {fname}: .y4m clips are synthesised, not scored")
         cat = [np.concatenate(c) for c in cols] if clips else None
         res = dict(clips=clips, summary=summarize(*cat[:5], **dict(zip(extra, cat[5:]))) if clips else None)
         if scorer:

@@ -433,6 +433,131 @@ def frame_msssim(pred, gt, scales=5):
     return out, parts
 
 
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}  # (Kr, Kb)
+
+
+def yuv_tables(matrix="bt601", full_range=False):
+    """The integer tables of dvie_synth_yuv2rgb / dvie_synth_rgb2yuv -> (inverse, forward, yo):
+    inverse = (IY, IRV, IBU, IGU, IGV), forward = (FY[3], FU[3], FV[3]) flattened, every entry
+    round(65536 * x) as a Python int, yo the luma offset.  Kr, Kb from the matrix ("bt601",
+    "bt709"), Kg = 1 - Kr - Kb; limited range sy = 219/255, sc = 224/255, yo = 16, full range
+    sy = sc = 1, yo = 0.  The only place the floats become integers (include/dvie.h has the
+    formulas the integers enter)."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix {matrix!r} must be one of {', '.join(YUV_MATRICES)}")
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    sy, sc, yo = (1.0, 1.0, 0) if full_range else (219.0 / 255.0, 224.0 / 255.0, 16)
+    q = lambda x: int(round(65536.0 * x))  # noqa: E731
+    inverse = (q(1.0 / sy), q(2.0 * (1.0 - kr) / sc), q(2.0 * (1.0 - kb) / sc),
+               q(2.0 * kb * (1.0 - kb) / (kg * sc)), q(2.0 * kr * (1.0 - kr) / (kg * sc)))
+    fu, fv = sc / (2.0 * (1.0 - kb)), sc / (2.0 * (1.0 - kr))
+    forward = (q(sy * kr), q(sy * kg), q(sy * kb),
+               q(-kr * fu), q(-kg * fu), q((1.0 - kb) * fu),
+               q((1.0 - kr) * fv), q(-kg * fv), q(-kb * fv))
+    return inverse, forward, yo
+
+
+def _yuv_layout(colourspace, what):
+    """DVIE_YUV_420 / DVIE_YUV_444 of a Y4M colourspace tag (Cmono has no chroma to convert)"""
+    from .video_io import layout_of
+    lay = layout_of(colourspace)
+    if lay == "mono":
+        raise ValueError(f"{what}: {colourspace} has no chroma; its Y plane is the first H * W bytes of a frame")
+    return L.YUV_420 if lay == "420" else L.YUV_444
+
+
+def _yuv_call(fn, what, yuv, yuv_stride, rgb_ptr, rgb_stride, n, H, W, layout, table, yo, dev):
+    d = L.SynthYuvDesc()
+    d.yuv, d.rgb, d.yuv_stride, d.rgb_stride, d.rgb_row_stride = yuv, rgb_ptr, yuv_stride, rgb_stride, 3 * W
+    d.n, d.h, d.w, d.layout, d.yo = n, H, W, layout, yo
+    for k, v in enumerate(table):
+        d.table[k] = v
+    L.check(fn(ctypes.byref(d), L.stream_ptr(dev)), what)
+
+
+def _packed_check(t, fb, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != fb or t.shape[0] < 1 \
+            or (t.stride(1) != 1 and fb != 1) or (t.shape[0] > 1 and t.stride(0) < fb):
+        raise ValueError(f"{what}: uint8 (N, {fb}) packed frames with contiguous rows, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+
+
+def yuv_to_rgb(packed, H, W, colourspace, matrix="bt601", full_range=False, out=None):
+    """Packed Y'CbCr frames `packed` (N, frame_bytes(W, H, colourspace)), uint8 on the device, rows
+    contiguous and any row stride -> uint8 RGB (N, H, W, 3) (dvie_synth_yuv2rgb: one launch, integer
+    arithmetic, nearest chroma upsampling for the 4:2:0 colourspaces).  out: a contiguous
+    (N, H, W, 3) uint8 tensor to write instead of a new one."""
+    from .video_io import frame_bytes
+    L.require_gpu(packed)
+    layout = _yuv_layout(colourspace, "yuv_to_rgb")
+    _packed_check(packed, frame_bytes(W, H, colourspace), "packed")
+    N = packed.shape[0]
+    if out is None:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=packed.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous() or out.device != packed.device:
+        raise ValueError(f"out: a contiguous uint8 {(N, H, W, 3)} tensor on {packed.device}")
+    inverse, _, yo = yuv_tables(matrix, full_range)
+    _yuv_call(L.load().dvie_synth_yuv2rgb, "synth yuv2rgb", packed.data_ptr(), packed.stride(0), out.data_ptr(),
+              H * W * 3, N, H, W, layout, inverse, yo, packed.device)
+    return out
+
+
+def rgb_to_yuv(frames, colourspace, matrix="bt601", full_range=False, out=None):
+    """uint8 RGB device frames (..., H, W, 3) with up to two leading dimensions of any strides (the
+    slot-major views interpolate returns are read in place) -> packed Y'CbCr frames
+    (N, frame_bytes(W, H, colourspace)) in the order of the leading dimensions (dvie_synth_rgb2yuv;
+    4:2:0 chroma is taken on the sum of each 2x2 block).  out: a uint8 (N, frame_bytes) tensor with
+    contiguous rows and any row stride and alignment (a slice of a larger buffer) to write instead.
+    One launch when the leading dimensions collapse to one stride, otherwise one per index of the
+    shorter of the two."""
+    from .video_io import frame_bytes
+    L.require_gpu(frames)
+    layout = _yuv_layout(colourspace, "rgb_to_yuv")
+    if frames.dim() < 3 or frames.shape[-1] != 3:
+        raise ValueError(f"frames: uint8 (..., H, W, 3), got {tuple(frames.shape)}")
+    H, W = frames.shape[-3:-1]
+    n0, n1, s0, s1 = _lead_of(frames, (H, W, 3), "frames")
+    N, fb = n0 * n1, frame_bytes(W, H, colourspace)
+    if N < 1:
+        raise ValueError(f"frames: empty dimensions in {tuple(frames.shape)}")
+    if out is None:
+        out = torch.empty((N, fb), dtype=torch.uint8, device=frames.device)
+    else:
+        _packed_check(out, fb, "out")
+        if out.shape[0] != N or out.device != frames.device:
+            raise ValueError(f"out: {N} packed frames on {frames.device}, got {tuple(out.shape)} on {out.device}")
+    _, forward, yo = yuv_tables(matrix, full_range)
+    fn, src, dst, ds = L.load().dvie_synth_rgb2yuv, frames.data_ptr(), out.data_ptr(), out.stride(0)
+    args = (H, W, layout, forward, yo, frames.device)
+    if n0 == 1 or n1 == 1 or s0 == n1 * s1:  # one run of N frames
+        _yuv_call(fn, "synth rgb2yuv", dst, ds, src, s1 if n0 == 1 else (s0 if n1 == 1 else s1), N, *args)
+    elif n0 <= n1:  # a launch per row of the (n0, n1) grid
+        for i in range(n0):
+            _yuv_call(fn, "synth rgb2yuv", dst + i * n1 * ds, ds, src + i * s0, s1, n1, *args)
+    else:  # a launch per column
+        for j in range(n1):
+            _yuv_call(fn, "synth rgb2yuv", dst + j * ds, n1 * ds, src + j * s1, s0, n0, *args)
+    return out
+
+
+def window_plan(T, window):
+    """The windows a T-frame clip is interpolated in: [(t0, t1)], inclusive input-frame ranges of at
+    most `window` frames that share their boundary frame -- (0, N-1), (N-1, 2N-2), ... -- the last
+    one shorter when T - 1 is no multiple of window - 1, never fewer than two frames.  Interpolation
+    between two neighbouring inputs depends on those two only, so the windows' results, each without
+    its first slot after the first window, concatenate to the whole clip's.  T < 2 or window < 2:
+    ValueError."""
+    if T < 2 or window < 2:
+        raise ValueError(f"window_plan needs T >= 2 frames and window >= 2, got T={T}, window={window}")
+    out, t0 = [], 0
+    while t0 < T - 1:
+        t1 = min(t0 + window - 1, T - 1)
+        out.append((t0, t1))
+        t0 = t1
+    return out
+
+
 def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perceptual=None, msssim=None):
     """Score uint8 device frames `pred` (..., H, W, 3) against `gt` and, when both are given,
     label maps `pred_labels` (..., H, W) against `gt_labels` (dvie_synth_score: one fused pass
@@ -840,6 +965,46 @@ class VideoSynthesizer:
         fr, lb = self._roll(frames, labels, n_slots, [t * step for t in range(T)], sched,
                             keep=lambda s: levels > 0 and s % 2 == 0)
         return fr.transpose(0, 1), lb.transpose(0, 1)
+
+    def interpolate_stream(self, chunks, levels=1):
+        """interpolate() of a clip of any length in bounded memory: a generator over `chunks`, any
+        iterable of (frames (B, t, H, W, 3), labels (B, t, H, W)) uint8 device tensors with t >= 1,
+        the clip in order.  The last input frame of a chunk (its uint8 frame and label map) is
+        carried to the next; whenever carry + chunk holds at least two frames it goes through
+        interpolate(), and the result is yielded -- without its first slot when that slot (the
+        carried frame) was yielded before.  A first chunk of one frame is held and yields nothing.
+        Everything yielded, concatenated, has (T - 1) * 2**levels + 1 slots with the originals bit
+        for bit at the multiples of 2**levels, and equals, window by window, interpolate() of the
+        windows (window_plan); with max_batch = 1 it equals interpolate() of the whole clip (with a
+        larger max_batch the windowing changes which pairs share a forward: `chunks`).  Nothing
+        but the carried frame stays on the device between chunks (the plans and scratch of the
+        synthesiser aside); what is yielded belongs to the consumer.  Fewer than two frames in
+        all: ValueError when the input ends."""
+        carry, emitted, total = None, False, 0
+        for frames, labels in chunks:
+            self._check(frames, labels)
+            t = frames.shape[1]
+            if t < 1:
+                raise ValueError("interpolate_stream: a chunk needs at least one frame")
+            if carry is not None:
+                if frames.shape[0] != carry[0].shape[0] or frames.shape[2:] != carry[0].shape[2:] or \
+                        frames.device != carry[0].device:
+                    raise ValueError(f"interpolate_stream: a chunk of {tuple(frames.shape)} follows one of "
+                                     f"{tuple(carry[0].shape)}")
+                frames, labels = torch.cat([carry[0], frames], 1), torch.cat([carry[1], labels], 1)
+            total += t
+            carry = (frames[:, -1:].clone(), labels[:, -1:].clone())
+            if frames.shape[1] < 2:
+                continue  # (the first chunk was one frame: held)
+            out_f, out_l = self.interpolate(frames, labels, levels)
+            del frames, labels
+            if emitted:
+                out_f, out_l = out_f[:, 1:], out_l[:, 1:]
+            emitted = True
+            yield out_f, out_l
+            del out_f, out_l
+        if total < 2:
+            raise ValueError(f"interpolate_stream needs at least two frames, got {total}")
 
     def extrapolate(self, frames, labels, steps=1):
         """frames (B, 2, H, W, 3), labels (B, 2, H, W) -> the `steps` following frames and

@@ -1080,11 +1080,52 @@ typedef struct dvie_synth_msssim_desc {
 size_t dvie_synth_msssim_ws_bytes(const dvie_synth_msssim_desc* d);
 int dvie_synth_msssim(const dvie_synth_msssim_desc* d, void* stream);
 
+/*
+ * dvie_synth_yuv2rgb / dvie_synth_rgb2yuv: 8-bit planar Y'CbCr frames, packed as a YUV4MPEG2 file
+ * holds them, <-> uint8 RGB frames (synth.yuv_to_rgb / rgb_to_yuv; DESIGN.md "Streaming and Y4M").
+ * One launch takes all n frames.  Integer arithmetic only, so that every implementation agrees to
+ * the byte; `>>` is the arithmetic shift, clip is to [0, 255].
+ *
+ * Packed frame f starts at yuv + f*yuv_stride BYTES: the Y plane (h x w), then U and V.  layout
+ * DVIE_YUV_420: U and V are (ch x cw) = ((h+1)/2 x (w+1)/2), one sample per 2x2 block (the last
+ * block row / column of an odd size is 1 pixel high / wide; chroma siting is not modelled);
+ * DVIE_YUV_444: U and V are (h x w).  RGB frame f starts at rgb + f*rgb_stride BYTES, its row y at
+ * + y*rgb_row_stride, a row w*3 contiguous bytes.  No alignment is assumed of either side: runs of 8
+ * pixels whose addresses are 8-byte aligned move as whole 8-byte vectors, everything else bytewise.
+ *
+ * yuv2rgb reads table[0..4] = (IY, IRV, IBU, IGU, IGV) and yo (synth.yuv_tables):
+ *   y = Y - yo, u = U - 128, v = V - 128 (4:2:0: the block's one sample for each of its pixels)
+ *   R = clip((IY*y + IRV*v + 32768) >> 16)
+ *   G = clip((IY*y - IGU*u - IGV*v + 32768) >> 16)
+ *   B = clip((IY*y + IBU*u + 32768) >> 16)
+ * rgb2yuv reads table[0..8] = (FY[3], FU[3], FV[3]) and yo:
+ *   Y = clip(yo + ((FY . (R,G,B) + 32768) >> 16))
+ *   S = the sums of R, G, B over the n pixels of the chroma block that exist (n = 4, 2 or 1; 4:4:4: 1)
+ *   U = clip(128 + (((FU . S) * (4/n) + 131072) >> 18)), V likewise with FV.
+ * |table[k]| <= 2^18 and 0 <= yo <= 255 keep every intermediate inside int32.
+ * n >= 1, 1 <= h, w <= 2^16; for n > 1 the strides must not let frames overlap
+ * (yuv_stride >= the packed frame size, rgb_stride >= (h-1)*rgb_row_stride + 3*w); rgb_row_stride >= 3*w.
+ */
+#define DVIE_YUV_420 420
+#define DVIE_YUV_444 444
+
+typedef struct dvie_synth_yuv_desc {
+  uint8_t* yuv;
+  uint8_t* rgb;
+  long long yuv_stride;                 /* bytes between packed frames */
+  long long rgb_stride, rgb_row_stride; /* bytes between RGB frames / rows */
+  int n, h, w, layout, yo, pad0;
+  int table[12];
+} dvie_synth_yuv_desc;
+
+int dvie_synth_yuv2rgb(const dvie_synth_yuv_desc* d, void* stream);
+int dvie_synth_rgb2yuv(const dvie_synth_yuv_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
- * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim). */
+ * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim, synth_yuv). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

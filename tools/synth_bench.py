@@ -42,8 +42,15 @@
   legs alternating, three rounds, the median, with the ratio to frame_scores (the pyramid holds
   1.33 times the pixels of level 0).
 
+* colour conversion (--yuv): us per launch and TB/s of algorithmic bytes (4.5 B per pixel) of
+  synth.yuv_to_rgb and synth.rgb_to_yuv, 4:2:0, at 8x256x512 and 1x1080x1920 (where a call's host
+  cost exceeds the kernel's device time) and at 64x256x512 and 32x1080x1920, against the same
+  conversion composed from torch ops on the device (slicing, float matrix product, round,
+  repeat_interleave / avg_pool), rotating over buffer sets that exceed the Infinity Cache, the legs
+  alternating, three rounds, the median and the spread, with the ratio composed / kernel.
+
     python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json]
-                                [--two-stage | --score | --pad | --vgg | --msssim]
+                                [--two-stage | --score | --pad | --vgg | --msssim | --yuv]
 """
 import argparse
 import json
@@ -400,6 +407,70 @@ def msssim_numbers(dev, seconds):
     return out
 
 
+def composed_yuv_to_rgb(packed, H, W, mat, yo):
+    """4:2:0 packed frames -> uint8 RGB with torch ops: what the kernel replaces (float32, so not
+    bit-equal to the integer form; timing only)"""
+    n = packed.shape[0]
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    y = packed[:, :H * W].reshape(n, H, W).float() - yo
+    u = packed[:, H * W:H * W + ch * cw].reshape(n, ch, cw).float() - 128.0
+    v = packed[:, H * W + ch * cw:].reshape(n, ch, cw).float() - 128.0
+    u = u.repeat_interleave(2, 1).repeat_interleave(2, 2)[:, :H, :W]
+    v = v.repeat_interleave(2, 1).repeat_interleave(2, 2)[:, :H, :W]
+    return (torch.stack([y, u, v], -1) @ mat).round_().clamp_(0, 255).to(torch.uint8)
+
+
+def composed_rgb_to_yuv(rgb, mat, off):
+    """uint8 RGB (n, H, W, 3), H and W even -> 4:2:0 packed frames with torch ops (float32; timing only)"""
+    n, H, W, _ = rgb.shape
+    yuv = rgb.float() @ mat
+    y = (yuv[..., 0] + off).round_().clamp_(0, 255).to(torch.uint8).reshape(n, -1)
+    c = torch.nn.functional.avg_pool2d(yuv[..., 1:].permute(0, 3, 1, 2), 2)
+    c = (c + 128.0).round_().clamp_(0, 255).to(torch.uint8).reshape(n, -1)
+    return torch.cat([y, c], 1)
+
+
+def yuv_numbers(dev, seconds):
+    """yuv_to_rgb / rgb_to_yuv (4:2:0, bt601, limited range) against the torch compositions,
+    alternating, three rounds; buffer sets past the Infinity Cache"""
+    from deep_video_interpolation_extrapolation_amd.synth import rgb_to_yuv, yuv_tables, yuv_to_rgb
+    inv, fwd, yo = yuv_tables("bt601", False)
+    IY, IRV, IBU, IGU, IGV = (v / 65536.0 for v in inv)
+    m_inv = torch.tensor([[IY, IY, IY], [0.0, -IGU, IBU], [IRV, -IGV, 0.0]], device=dev)
+    m_fwd = (torch.tensor(fwd, dtype=torch.float32, device=dev) / 65536.0).reshape(3, 3).t().contiguous()
+    out = {}
+    # 8x256x512 and 1x1080x1920 take a few microseconds on the device, less than a call costs on the
+    # host; 64x256x512 and 32x1080x1920 (the slots of one window) show the kernels' own rate
+    for n, H, W in ((8, 256, 512), (1, 1080, 1920), (64, 256, 512), (32, 1080, 1920)):
+        npix = n * H * W
+        fb = H * W * 3 // 2
+        sets = (320 << 20) // (9 * npix // 2) + 1  # 4.5 B per pixel and set: more than the cache holds
+        packed = [torch.randint(0, 256, (n, fb), dtype=torch.uint8, device=dev) for _ in range(sets)]
+        rgb = [torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(sets)]
+        k = [0]
+
+        def rot(fn):
+            def run():
+                i = k[0] = (k[0] + 1) % sets
+                fn(i)
+            return run
+
+        legs = dict(yuv2rgb=rot(lambda i: yuv_to_rgb(packed[i], H, W, "C420", out=rgb[i])),
+                    rgb2yuv=rot(lambda i: rgb_to_yuv(rgb[i], "C420", "bt601", False, out=packed[i])),
+                    yuv2rgb_composed=rot(lambda i: composed_yuv_to_rgb(packed[i], H, W, m_inv, yo)),
+                    rgb2yuv_composed=rot(lambda i: composed_rgb_to_yuv(rgb[i], m_fwd, float(yo))))
+        rates = _alternate(legs, seconds)
+        row = {name: dict(us=1e6 / sorted(v)[1], runs_us=[1e6 / r for r in v], spread=(max(v) - min(v)) / sorted(v)[1],
+                          tbs=4.5 * npix * sorted(v)[1] / 1e12) for name, v in rates.items()}
+        row["buffer_sets"] = sets
+        for name in ("yuv2rgb", "rgb2yuv"):
+            row[f"{name}_composed_over_kernel"] = row[name + "_composed"]["us"] / row[name]["us"]
+        out[f"{n}x{H}x{W}"] = row
+        del packed, rgb
+        torch.cuda.empty_cache()
+    return out
+
+
 def pad_kernel_numbers(dev, seconds):
     """load_pad / finish_crop against load / finish on the same canvas, rotating over buffer sets of
     more than 2 GB in all (every launch streams from HBM).  GB/s are of algorithmic bytes: finish
@@ -576,7 +647,15 @@ def main():
     ap.add_argument("--pad", action="store_true", help="only the padded-canvas legs")
     ap.add_argument("--vgg", action="store_true", help="only the perceptual-score legs")
     ap.add_argument("--msssim", action="store_true", help="only the multi-scale SSIM legs")
+    ap.add_argument("--yuv", action="store_true", help="only the colour-conversion legs")
     a = ap.parse_args()
+    if a.yuv:
+        res = dict(yuv=yuv_numbers(torch.device("cuda:0"), a.seconds))
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.msssim:
         res = dict(msssim=msssim_numbers(torch.device("cuda:0"), a.seconds))
         print(json.dumps(res, indent=1))
