@@ -329,7 +329,7 @@ EXPORTS = [
     "dvie_synth_load", "dvie_synth_finish", "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_score_ws_bytes",
     "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits", "dvie_bn_partial_doubles",
     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks", "dvie_synth_msssim", "dvie_synth_msssim_ws_bytes",
-    "dvie_synth_yuv2rgb", "dvie_synth_rgb2yuv",
+    "dvie_synth_yuv2rgb", "dvie_synth_rgb2yuv", "dvie_conv_chain", "dvie_conv2d_chain", "dvie_ops_chain_pairs",
 ]
 
 _lib = None
@@ -382,6 +382,12 @@ def load():
             getattr(lib, name).argtypes = [vp]
             getattr(lib, name).restype = i32
         lib.dvie_run_ops.argtypes = [vp, i32, vp]
+        lib.dvie_conv_chain.argtypes = [vp, vp]
+        lib.dvie_conv_chain.restype = i32
+        lib.dvie_conv2d_chain.argtypes = [vp, vp, vp]
+        lib.dvie_conv2d_chain.restype = i32
+        lib.dvie_ops_chain_pairs.argtypes = [vp, i32, vp]
+        lib.dvie_ops_chain_pairs.restype = i32
         lib.dvie_loss_partial_count.argtypes = [vp]
         lib.dvie_loss_partial_count.restype = ctypes.c_size_t
         lib.dvie_warp_ws_floats.argtypes = [vp]

@@ -1018,6 +1018,22 @@ int conv1x1_zbits(const dvie_conv_desc& p) {
   return zb_reads(p);
 }
 
+// The routing as the chained launch (conv_chain.hip) asks for it, so that its predicate follows
+// the single launches: -1 when this file does not take the launch, else 10 * TMC + NS of the
+// tile shape (T_WIDE: 42); *zb: bit 0 zb_reads, bit 1 zb_writes.
+int conv1x1_route(const dvie_conv_desc& p, int* zb) {
+  *zb = 0;
+  if (!takes_1x1(p)) return -1;
+  *zb = (zb_reads(p) ? 1 : 0) | (zb_writes(p) ? 2 : 0);
+  switch (tile_1x1(p)) {
+    case T_2_1: return 21;
+    case T_2_3: return 23;
+    case T_4_3: return 43;
+    case T_4_1: return 41;
+    default: return 42;
+  }
+}
+
 // Returns true when the 1x1 GEMM kernel took the launch.
 bool conv1x1_launch(const dvie_conv_desc& p, hipStream_t s) {
   if (!takes_1x1(p)) return false;

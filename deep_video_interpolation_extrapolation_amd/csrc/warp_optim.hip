@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 
@@ -682,11 +683,91 @@ struct LaneRun {
 };
 }  // namespace
 
+// DVIE_CHAIN=0: no chained 1x1 launches (conv_chain.hip), every op runs as its own launch;
+// read per call
+static bool chain_on() {
+  const char* e = getenv("DVIE_CHAIN");
+  return !(e && *e == '0');
+}
+
+// The byte spans a weight-lane op reads and writes, for the chain pairing's look-ahead.
+// false: a kind the pairing does not know.
+struct OpSpan {
+  const void* p;
+  unsigned long long bytes;
+};
+static bool weight_op_spans(const dvie_op& o, std::vector<OpSpan>& v) {
+  auto reduce = [&](const dvie_wreduce_desc& d) {
+    v.push_back({d.ws, (unsigned long long)d.splits * d.ws_rows * d.ws_k * 4ull});
+    v.push_back({d.dw, (unsigned long long)d.cout_p * d.cin_p * d.kh_n * d.kw_n * 4ull});
+  };
+  switch (o.kind) {
+    case DVIE_OP_WGRAD: {
+      const dvie_wgrad_desc& d = o.u.wgrad;
+      const unsigned long long es = d.dtype == DVIE_BF16 ? 2 : 4;
+      const unsigned long long row = (unsigned long long)(d.ws_taps > 0 ? d.ws_taps : d.th * d.tw) * d.c;
+      v.push_back({d.g, ((unsigned long long)d.n * d.oh * d.ow - 1) * d.g_ld * es + d.cout * es});
+      v.push_back({d.x, ((unsigned long long)d.n * d.ih * d.iw - 1) * d.x_ld * es + d.c * es});
+      v.push_back({d.ws, (unsigned long long)dvie_wgrad_slabs(&d) * d.cout * row * 4ull});
+      if (d.bws) v.push_back({d.bws, (unsigned long long)dvie_wgrad_bias_slabs(&d) * d.cout * 4ull});
+      return true;
+    }
+    case DVIE_OP_WREDUCE: reduce(o.u.wreduce); return true;
+    case DVIE_OP_WREDUCE_MULTI:
+      for (int k = 0; k < o.u.wreduce_multi.n; ++k) reduce(o.u.wreduce_multi.descs[k]);
+      return true;
+    case DVIE_OP_COLSUM: {
+      const dvie_colsum_desc& d = o.u.colsum;
+      const unsigned long long es = d.dtype == DVIE_BF16 ? 2 : 4;
+      v.push_back({d.g, (unsigned long long)(d.rows - 1) * d.g_ld * es + d.c * es});
+      v.push_back({d.ws, (unsigned long long)d.splits * d.c * 4ull});
+      return true;
+    }
+    default: return false;
+  }
+}
+
 extern "C" {
+
+int dvie_ops_chain_pairs(const dvie_op* ops, int n, int* partner) {
+  int pairs = 0;
+  for (int i = 0; i < n; ++i) partner[i] = -1;
+  if (!chain_on()) return 0;
+  std::vector<OpSpan> sp;
+  for (int i = 0; i + 1 < n; ++i) {
+    if (partner[i] >= 0 || ops[i].kind != DVIE_OP_CONV || ops[i].lane != 0) continue;
+    int j = i + 1;
+    while (j < n && ops[j].lane == 1) ++j;  // the next op of the caller's stream
+    if (j >= n || ops[j].kind != DVIE_OP_CONV || ops[j].lane != 0) continue;
+    const dvie_conv_desc& a = ops[i].u.conv;
+    const dvie_conv_desc& b = ops[j].u.conv;
+    if (!dvie_conv_chain(&a, &b)) continue;
+    // the skipped weight-lane ops run after b instead of before it: none may touch b's output
+    const uintptr_t y0 = (uintptr_t)b.y;
+    const unsigned long long yb = ((unsigned long long)b.n * b.yh * b.yw - 1) * b.y_ld * 2ull + b.cout * 2ull;
+    bool ok = true;
+    sp.clear();
+    for (int k = i + 1; k < j && ok; ++k) ok = weight_op_spans(ops[k], sp);
+    for (size_t k = 0; k < sp.size() && ok; ++k)
+      if (sp[k].p && sp[k].bytes && (uintptr_t)sp[k].p < y0 + yb && y0 < (uintptr_t)sp[k].p + sp[k].bytes) ok = false;
+    if (!ok) continue;
+    partner[i] = j;
+    partner[j] = i;
+    ++pairs;
+  }
+  return pairs;
+}
 
 int dvie_run_ops(const dvie_op* ops, int n, void* stream) {
   LaneRun lr;
   lr.main = (hipStream_t)stream;
+  // chained pairs (a, b): a's turn runs both in one launch on the caller's stream, the
+  // weight-lane ops between them follow in their order, b's turn is skipped
+  std::vector<int> partner;
+  if (n > 1 && chain_on()) {
+    partner.resize(n);
+    if (dvie_ops_chain_pairs(ops, n, partner.data()) == 0) partner.clear();
+  }
   // Under stream capture every op stays on the caller's stream: the weight lane's per-run
   // waits become graph edges, and the replayed graph ran 23-33% slower than the one-stream
   // capture (C2 43.7 vs 35.4 ms, C5 224 vs 169 ms per step, profiles/r04v/); eagerly the lane
@@ -733,6 +814,10 @@ int dvie_run_ops(const dvie_op* ops, int n, void* stream) {
     static const long long skip_kinds = getenv("DVIE_SKIP_KINDS") ? atoll(getenv("DVIE_SKIP_KINDS")) : 0;
     if ((skip_kinds >> o.kind) & 1) continue;
 #endif
+    if (!partner.empty() && partner[i] >= 0) {
+      if (partner[i] < i) continue;  // ran with its partner
+      rc = dvie_conv2d_chain(&o.u.conv, &ops[partner[i]].u.conv, s);
+    } else
     switch (o.kind) {
       case DVIE_OP_CONV: rc = dvie_conv2d_fwd(&o.u.conv, s); break;
       case DVIE_OP_WGRAD: rc = dvie_conv2d_wgrad(&o.u.wgrad, s); break;

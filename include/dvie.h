@@ -111,6 +111,23 @@ int dvie_conv2d_fwd(const dvie_conv_desc* d, void* stream);
  * multi-K-step ring 1x1 kernel: +8% on heads.0), for the caller to weigh against its readers. */
 int dvie_conv_zbits(const dvie_conv_desc* d);
 
+/* Two back-to-back 1x1 convolutions on the same pixels as ONE launch (conv1x1_chain_kernel;
+ * layer1's Bottlenecks, nets/HRNet.py:66-85: conv3(N) -> conv1(N+1) forward, the data gradient
+ * of conv1(N+1) -> that of conv3(N) backward).  b reads a's output from on-chip memory; a's
+ * output (and bitmap) is still stored.  y, the bitmap and b's y are byte for byte what
+ * dvie_conv2d_fwd(a) followed by dvie_conv2d_fwd(b) give.
+ * dvie_conv_chain: nonzero iff the pair runs chained.  Both are bf16 1x1 stride-1 convs with
+ * identity output placement, bf16 output and beta == 0 on the same n x oh x ow grid;
+ * b->x == a->y, b->x_ld == a->y_ld, a->c <= 64 (a multiple of 8), a->cout == b->c == 256,
+ * b->cout == 64; act / dact are none, ReLU or LeakyReLU, at most one of them per op (a: bias,
+ * residual, activation with the bitmap written when dvie_conv_zbits(a) says so, or residual +
+ * derivative from the bitmap or z as the single launch would take it; b: bias, activation or
+ * derivative from z, no residual, no bitmap); no output of one op overlaps an operand or output
+ * of the other (but a->y as b->x); every tensor's byte span stays below 4 GiB.
+ * dvie_conv2d_chain: launches the pair; DVIE_EINVAL (dvie_last_error) when dvie_conv_chain is 0. */
+int dvie_conv_chain(const dvie_conv_desc* a, const dvie_conv_desc* b);
+int dvie_conv2d_chain(const dvie_conv_desc* a, const dvie_conv_desc* b, void* stream);
+
 /*
  * Weight gradient of the convolution above (replaces nn.Conv2d backward-weight):
  *   part[s][co][t*c + ci] = sum_{pix in split s} g[pix][co] * x[pix + tap t][ci]
@@ -1122,6 +1139,17 @@ int dvie_synth_yuv2rgb(const dvie_synth_yuv_desc* d, void* stream);
 int dvie_synth_rgb2yuv(const dvie_synth_yuv_desc* d, void* stream);
 
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
+
+/* The pairs of ops dvie_run_ops(ops, n) runs as chained launches (host only, nothing is
+ * launched): partner[i] = j and partner[j] = i for a pair, -1 for every other op; returns the
+ * number of pairs.  Op i (a conv on lane 0) pairs with the next lane-0 op j when every op
+ * between them is a weight-lane op of a known kind (weight gradient, reduction, column sum),
+ * dvie_conv_chain(&ops[i].u.conv, &ops[j].u.conv) holds and none of the ops between reads or
+ * writes ops[j]'s output.  The executor runs the pair at i's turn on the caller's stream, then
+ * the ops between them in their order, and goes on after j.  A pair split across two
+ * dvie_run_ops calls runs as two launches, as does every op run one at a time.
+ * DVIE_CHAIN=0 (environment, read per call): no pairs. */
+int dvie_ops_chain_pairs(const dvie_op* ops, int n, int* partner);
 
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
