@@ -199,6 +199,21 @@ class SynthYuvDesc(ctypes.Structure):
     ]
 
 
+class SynthSceneDesc(ctypes.Structure):
+    _fields_ = [
+        ("frames", vp), ("sad", vp), ("hdiff", vp), ("cut", vp), ("ws", vp),
+        ("s0", i64), ("s1", i64), ("sad_min", i64), ("hist_min", i64),
+        ("n0", i32), ("n1", i32), ("h", i32), ("w", i32),
+    ]
+
+
+class SynthCutFillDesc(ctypes.Structure):
+    _fields_ = [
+        ("slots", vp), ("cut", vp), ("s0", i64), ("s1", i64), ("nbytes", i64),
+        ("n0", i32), ("n1", i32), ("levels", i32), ("pad0", i32),
+    ]
+
+
 class CosFeatDesc(ctypes.Structure):
     _fields_ = [
         ("feat", vp), ("ws", vp), ("out", vp), ("ld", i64),
@@ -315,7 +330,7 @@ _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, 
         104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc, 107: SynthScoreDesc,
         108: SynthLoadPadDesc, 109: SynthFinishCropDesc, 110: SynthVggLoadDesc}
 # descriptors added after the set tests/test_perceptual_cpu.py pins for _ABI; load() checks both tables
-_ABI_MORE = {111: SynthMsssimDesc, 112: SynthYuvDesc}
+_ABI_MORE = {111: SynthMsssimDesc, 112: SynthYuvDesc, 113: SynthSceneDesc, 114: SynthCutFillDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -330,6 +345,7 @@ EXPORTS = [
     "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits", "dvie_bn_partial_doubles",
     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks", "dvie_synth_msssim", "dvie_synth_msssim_ws_bytes",
     "dvie_synth_yuv2rgb", "dvie_synth_rgb2yuv", "dvie_conv_chain", "dvie_conv2d_chain", "dvie_ops_chain_pairs",
+    "dvie_synth_scene", "dvie_synth_scene_ws_bytes", "dvie_synth_cutfill",
 ]
 
 _lib = None
@@ -367,7 +383,7 @@ def load():
                      "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
                      "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop",
                      "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_synth_msssim", "dvie_synth_yuv2rgb",
-                     "dvie_synth_rgb2yuv"):
+                     "dvie_synth_rgb2yuv", "dvie_synth_scene", "dvie_synth_cutfill"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]
@@ -400,6 +416,8 @@ def load():
         lib.dvie_synth_score_ws_bytes.restype = ctypes.c_size_t
         lib.dvie_synth_msssim_ws_bytes.argtypes = [vp]
         lib.dvie_synth_msssim_ws_bytes.restype = ctypes.c_size_t
+        lib.dvie_synth_scene_ws_bytes.argtypes = [vp]
+        lib.dvie_synth_scene_ws_bytes.restype = ctypes.c_size_t
         lib.dvie_adamax.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]
         lib.dvie_scale.argtypes = [vp, i64, f32, vp]
         lib.dvie_adam.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]

@@ -882,6 +882,8 @@ size_t dvie_abi_sizeof(int which) {
     case 110: return sizeof(dvie_synth_vgg_load_desc);
     case 111: return sizeof(dvie_synth_msssim_desc);
     case 112: return sizeof(dvie_synth_yuv_desc);
+    case 113: return sizeof(dvie_synth_scene_desc);
+    case 114: return sizeof(dvie_synth_cutfill_desc);
     default: return 0;
   }
 }

@@ -43,6 +43,18 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
                             id); a .y4m clip is written as synth/{rgb,seg,vis_seg}/<name>.y4m.  Y4M has
                             no tag for the matrix: bt601 (default) is what swscale writes and assumes
                             for an untagged stream; the range follows the file's XCOLORRANGE tag
+  --synth_scd               --split test, INTER: scene-cut detection (synth.SceneCuts; off by default).  A
+                            neighbouring pair of input frames is a cut when its mean absolute luma
+                            difference reaches --synth_scd_mad AND its 32-bin luma histogram distance
+                            reaches --synth_scd_hist; the 2**K - 1 slots between the two frames then hold
+                            the nearer input frame and label map (the midpoint the earlier one's) instead
+                            of the network's blend -- in a .y4m clip the input's own packed bytes -- and
+                            one log line per clip names the input frames the cuts follow.  EXTRA predicts
+                            as without it and warns when a clip's last two frames are a cut;
+                            --synth_eval ignores it
+  --synth_scd_mad F         the mean absolute luma difference of a cut, 0..255 (default 30)
+  --synth_scd_hist F        the histogram distance of a cut, 0..1 (default 0.25).  Both defaults are
+                            provisional: they have not been validated on real footage
 """
 import argparse
 
@@ -55,6 +67,16 @@ def _window(text):
     if n == 1 or n < 0:
         raise argparse.ArgumentTypeError(f"--synth_window {n}: a window holds at least 2 input frames (0 = the whole clip)")
     return n
+
+
+def _unit_range(flag, hi):
+    """a float option in 0..hi"""
+    def parse(text):
+        v = float(text)
+        if not 0 <= v <= hi:  # (NaN fails too)
+            raise argparse.ArgumentTypeError(f"{flag} {text}: must be in 0..{hi}")
+        return v
+    return parse
 
 
 # (flag, dest, kind, default, choices)  kind: str/int/float/bool(store_true)
@@ -112,6 +134,9 @@ GLOBAL = [
     ("--synth_pad", "synth_pad", str, "none", ["none", "replicate"]),
     ("--synth_window", "synth_window", _window, 0, None),
     ("--synth_yuv", "synth_yuv", str, "bt601", ["bt601", "bt709"]),
+    ("--synth_scd", "synth_scd", bool, False, None),
+    ("--synth_scd_mad", "synth_scd_mad", _unit_range("--synth_scd_mad", 255), 30.0, None),
+    ("--synth_scd_hist", "synth_scd_hist", _unit_range("--synth_scd_hist", 1), 0.25, None),
 ]
 
 # second-stage flags of the reference's INTER sub-command (options/options.py:296-380);

@@ -166,9 +166,17 @@ class ExtraTrainer(InterTrainer):
 
     _streams = False  # extrapolation reads a clip's last two frames: --synth_window does not apply
 
-    def _synthesize(self, syn, frames, labels):
-        """--split test, extrapolation: --num_pred_step frames after the clip's last two"""
-        return syn.extrapolate(frames[:, -2:], labels[:, -2:], steps=getattr(self.args, "num_pred_step", 1))
+    def _synthesize(self, syn, frames, labels, clip=""):
+        """--split test, extrapolation: --num_pred_step frames after the clip's last two.  --synth_scd
+        changes nothing of the prediction: a warning is logged when those two frames are a cut"""
+        from ..synth import scene_cuts
+        scene = self._scene()
+        cut = scene_cuts(frames[:, -2:], scene.mad, scene.hist) if scene is not None else None
+        out = syn.extrapolate(frames[:, -2:], labels[:, -2:], steps=getattr(self.args, "num_pred_step", 1))
+        if cut is not None and bool(cut.cpu().any()):
+            self.log.warning(f"synth: {clip}: the last two frames are a scene cut: the prediction continues a "
+                             "motion that is not there")
+        return out
 
     def _score(self, syn, frames, labels, clip, perceptual=None, msssim=None):
         """--split test --synth_eval, extrapolation: the clip's first two frames are the inputs,

@@ -364,9 +364,29 @@ class InterTrainer:
         except FrameSizeError as e:
             raise FrameSizeError(f"{e} (--synth_pad replicate takes clips of any size)") from None
 
-    def _synthesize(self, syn, frames, labels):
-        """--split test, interpolation: --synth_levels frame-rate doublings of the whole clip"""
-        return syn.interpolate(frames, labels, levels=getattr(self.args, "synth_levels", 1))
+    def _scene(self):
+        """the synth.SceneCuts of --synth_scd (--synth_scd_mad, --synth_scd_hist), or None"""
+        from ..synth import SceneCuts
+        a = self.args
+        if not getattr(a, "synth_scd", False):
+            return None
+        return SceneCuts(mad=getattr(a, "synth_scd_mad", 30.0), hist=getattr(a, "synth_scd_hist", 0.25))
+
+    def _log_cuts(self, clip, flags):
+        """one line per clip: `flags`, the host flags of its neighbouring input pairs in order"""
+        at = [t for t, c in enumerate(flags) if c]
+        self.log.info("synth: {}: {} scene cut{} after input frame{} {}".format(
+            clip, len(at), "" if len(at) == 1 else "s", "" if len(at) == 1 else "s", at))
+
+    def _synthesize(self, syn, frames, labels, clip=""):
+        """--split test, interpolation: --synth_levels frame-rate doublings of the whole clip; with
+        --synth_scd frames are held across the detected cuts, which are logged"""
+        scene = self._scene()
+        if scene is None:
+            return syn.interpolate(frames, labels, levels=getattr(self.args, "synth_levels", 1))
+        out_f, out_l, cuts = syn.interpolate(frames, labels, levels=getattr(self.args, "synth_levels", 1), scene=scene)
+        self._log_cuts(clip, cuts[0].cpu().tolist())
+        return out_f, out_l
 
     _streams = True  # --synth_window applies: interpolation runs in windows (ExtraTrainer: False)
 
@@ -402,7 +422,7 @@ class InterTrainer:
             imgs = np.stack([np.asarray(Image.open(os.path.join(img_dir, clip, f)).convert("RGB")) for f in names])
             labs = np.stack([np.asarray(Image.open(os.path.join(seg_dir, clip, f)).convert("L")) for f in names])
             frames, labels = self._on_clip(self._synthesize, syn, torch.from_numpy(imgs)[None].to(self.device),
-                                           torch.from_numpy(labs)[None].to(self.device))
+                                           torch.from_numpy(labs)[None].to(self.device), clip)
             frames, labels = frames[0].cpu().numpy(), labels[0].cpu().numpy()
             vis = palette[np.minimum(labels, len(palette) - 1)]  # (ids past the classes: "none")
             for sub, arr in (("rgb", frames), ("seg", labels), ("vis_seg", vis)):
@@ -441,23 +461,37 @@ class InterTrainer:
             originals.extend(a.unbind(0))
         return frames[None], b[:, :H * W].reshape(-1, H, W).contiguous()[None]
 
-    def _pack_y4m(self, src, out_f, out_l, palette, originals=None, first=0, step=0):
+    def _pack_y4m(self, src, out_f, out_l, palette, originals=None, first=0, step=0, cuts=None, hold=None):
         """frames (S, H, W, 3) and labels (S, H, W) of one Y4M clip on the device (any stride over S)
         -> what Y4MSink.write takes, on the host: the packed frames in the input's colourspace, the
         label maps, and their palette colouring packed as C444.  step >= 1: slots first, first +
         step, ... are input frames and get their own packed bytes, copied from the deque
         `originals`; only the other slots go through synth.rgb_to_yuv, each residue modulo step
-        as one strided run read and written in place.  step 0: every slot is converted."""
-        from ..synth import rgb_to_yuv
+        as one strided run read and written in place.  step 0: every slot is converted.
+        cuts: the window's flags (1, t - 1) of interpolate_stream(..., scene=) -> the packed slots
+        between a flagged pair are synth.cut_fill's copies of the neighbouring input's own packed
+        bytes, not a conversion of the held RGB frame.  The fill needs the window's leading input
+        slot: `hold`, a one-element list, carries the packed bytes of the last input frame from one
+        window to the next, where they stand in front of the block while it is filled."""
+        from ..synth import cut_fill, rgb_to_yuv
         from ..video_io import frame_bytes
         S, H, W = out_l.shape
         cs, full, matrix = src.rgb.colourspace, src.rgb.full_range, getattr(self.args, "synth_yuv", "bt601")
-        pk = torch.empty((S, frame_bytes(W, H, cs)), dtype=torch.uint8, device=out_f.device)
+        lead = int(cuts is not None and hold[0] is not None)  # (the window came without its first slot)
+        pkx = torch.empty((S + lead, frame_bytes(W, H, cs)), dtype=torch.uint8, device=out_f.device)
+        pk = pkx[lead:]
+        if lead:
+            pkx[0].copy_(hold[0])
         if step:
             for i in range(first, S, step):
-                pk[i].copy_(originals.popleft())
+                o = originals.popleft()
+                pk[i].copy_(o)
+                if hold is not None:
+                    hold[0] = o
         for r in ([0] if not step else [r for r in range(min(step, S)) if r != first]):
             rgb_to_yuv(out_f[r::max(step, 1)], cs, matrix, full, out=pk[r::max(step, 1)])
+        if cuts is not None and step > 1:
+            cut_fill(pkx[None], cuts, step.bit_length() - 1)
         vis = palette[out_l.clamp(max=palette.shape[0] - 1).long()]  # (ids past the classes: "none")
         vis = rgb_to_yuv(vis, "C444", matrix, full)
         return pk.cpu().numpy(), out_l.reshape(S, H * W).cpu().numpy(), vis.cpu().numpy()
@@ -468,7 +502,10 @@ class InterTrainer:
         to the device, runs VideoSynthesizer.interpolate_stream and copies the result back, a
         writer thread encodes and writes it; both queues hold at most two windows.  Every HIP call
         is made here.  Output slots are numbered across windows; for a .y4m clip the slots at the
-        multiples of 2**synth_levels are the input's packed bytes, written back untouched."""
+        multiples of 2**synth_levels are the input's packed bytes, written back untouched.  With
+        --synth_scd the windows come with their cut flags: the held slots of a .y4m clip are the
+        neighbouring input's packed bytes (_pack_y4m), the flags reach the host with the window's
+        other copies, and one log line names the clip's cuts."""
         import collections
         import time
         from ..synth import FrameSizeError
@@ -483,19 +520,23 @@ class InterTrainer:
                            src.rgb.full_range)
             palette = torch.from_numpy(palette).to(self.device)
         originals = collections.deque()
+        scene, flags, hold = self._scene(), [], [None]
         t_start, g0 = time.perf_counter(), 0
         try:
             with Prefetcher(src.chunks(window)) as reader, BackgroundWriter(sink.write) as writer:
                 on_device = (self._upload(src, host, originals if src.kind == "y4m" else None) for host in reader)
                 try:
-                    for out_f, out_l in syn.interpolate_stream(on_device, levels=levels):
+                    for out_f, out_l, *cuts in syn.interpolate_stream(on_device, levels=levels, scene=scene):
                         S = out_f.shape[1]
                         if src.kind == "png":
                             writer.put((g0, out_f[0].cpu().numpy(), out_l[0].cpu().numpy()))
                         else:
-                            writer.put(self._pack_y4m(src, out_f[0], out_l[0], palette, originals, (-g0) % step, step))
+                            writer.put(self._pack_y4m(src, out_f[0], out_l[0], palette, originals, (-g0) % step, step,
+                                                      *((cuts[0], hold) if cuts else ())))
+                        if cuts:
+                            flags += cuts[0][0].cpu().tolist()
                         g0 += S
-                        del out_f, out_l
+                        del out_f, out_l, cuts
                 except FrameSizeError as e:
                     raise FrameSizeError(f"{e} (--synth_pad replicate takes clips of any size)") from None
                 torch.cuda.synchronize(self.device)
@@ -503,6 +544,8 @@ class InterTrainer:
         finally:
             sink.close()
         t_end = time.perf_counter()
+        if scene is not None:
+            self._log_cuts(src.name, flags)
         self.log.info("synth: {}: {} slots in {:.3f} s ({:.1f} slots/s); reader busy {:.3f} s, this thread waited for it "
                       "{:.3f} s and for the writer {:.3f} s, writer busy {:.3f} s ({:.3f} s after the last window)".format(
                           src.name, g0, t_end - t_start, g0 / max(t_end - t_start, 1e-9), reader.busy, reader.waited,
@@ -515,7 +558,7 @@ class InterTrainer:
         host = list(src.chunks(0))
         if not host or host[0][0].shape[0] < 2:
             raise ValueError(f"{src.name}: a clip needs at least two frames")
-        frames, labels = self._on_clip(self._synthesize, syn, *self._upload(src, host[0]))
+        frames, labels = self._on_clip(self._synthesize, syn, *self._upload(src, host[0]), src.name)
         sink = Y4MSink(root, src.name, src.width, src.height, src.rgb.fps, src.rgb.colourspace, src.rgb.full_range)
         try:
             sink.write(self._pack_y4m(src, frames[0], labels[0], torch.from_numpy(palette).to(self.device)))
@@ -555,6 +598,8 @@ class InterTrainer:
         from PIL import Image
         from ..synth import PerceptualScorer, msssim_check, summarize, vgg_region
         a = self.args
+        if getattr(a, "synth_scd", False):
+            self.log.info("synth_eval: --synth_scd is ignored: every held-out frame is scored against its original")
         syn = self._synthesizer()
         scorer = PerceptualScorer(max_batch=max(1, a.batch_size)) if getattr(a, "synth_vgg", False) else None
         scales = getattr(a, "synth_msssim", 0) or None

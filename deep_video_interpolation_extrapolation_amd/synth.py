@@ -46,6 +46,12 @@ Scoring: `frame_scores` (PSNR, SSIM, label agreement: dvie_synth_score) and, opt
 buffer of my_vgg's forward-only, arena-allocated scoring plan from the uint8 frames, and the
 plan's own cosfeat ops reduce the five feature maps to one float64 per frame; and
 `frame_msssim`, the per-frame multi-scale SSIM over an exact integer pyramid (dvie_synth_msssim).
+
+Scene cuts (opt-in, `SceneCuts`): `scene_stats` reduces every neighbouring pair of input frames to
+two integers (luma SAD, 32-bin luma histogram distance: dvie_synth_scene), `scene_cuts` compares
+them with two integer limits on the device, and after the unchanged rollout `cut_fill`
+(dvie_synth_cutfill) overwrites the slots between a flagged pair with copies of the nearer input
+frame and label map.  The flags never visit the host on the way.
 """
 import ctypes
 
@@ -558,6 +564,120 @@ def window_plan(T, window):
     return out
 
 
+def scene_stats(frames):
+    """The scene-cut statistic of uint8 device clips `frames` (B, T, H, W, 3), T >= 2, any strides
+    over B and T (the frame-level dimensions contiguous) -> (sad, hdiff), int64 device tensors
+    (B, T - 1): per neighbouring pair the sum of |Y_t - Y_t+1| over the pixels and the sum over
+    32 bins of |h_t - h_t+1|, Y = (77 R + 150 G + 29 B + 128) >> 8 and h the histogram of Y >> 3
+    (dvie_synth_scene: one pass that reads every frame once, a finalize launch; exact integers, no
+    host synchronisation)."""
+    return _scene_call(frames, None)[:2]
+
+
+def scene_limits(H, W, mad, hist):
+    """The two integer limits a pair of (H, W) frames is compared with -> (sad_min, hist_min) =
+    (ceil(mad * H * W), ceil(hist * 2 * H * W)), Python ints: the only place a float becomes an
+    integer.  mad: the mean absolute luma difference in 0..255; hist: the histogram distance in
+    0..1 (ValueError outside)."""
+    import math
+    if not 0 <= mad <= 255 or not 0 <= hist <= 1:
+        raise ValueError(f"scene_limits: mad={mad} must be in 0..255 and hist={hist} in 0..1")
+    if H < 1 or W < 1:
+        raise ValueError(f"scene_limits: H={H} and W={W} must be at least 1")
+    return int(math.ceil(mad * H * W)), int(math.ceil(hist * 2 * H * W))
+
+
+def _scene_call(frames, limits):
+    """scene_stats, and with limits = (sad_min, hist_min) the flags of the finalize launch too ->
+    (sad, hdiff, cut or None)"""
+    L.require_gpu(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 or frames.shape[1] < 2 or \
+            min(frames.shape) < 1:
+        raise ValueError(f"frames: uint8 (B, T, H, W, 3) with T >= 2, got {tuple(frames.shape)} {frames.dtype}")
+    B, T, H, W, _ = frames.shape
+    d = L.SynthSceneDesc()
+    d.n0, d.n1, d.s0, d.s1 = _lead_of(frames, (H, W, 3), "frames")
+    d.frames, d.h, d.w = frames.data_ptr(), H, W
+    dev = frames.device
+    sad = torch.empty((B, T - 1), dtype=torch.int64, device=dev)
+    hdiff = torch.empty((B, T - 1), dtype=torch.int64, device=dev)
+    cut = None
+    if limits is not None:
+        cut = torch.empty((B, T - 1), dtype=torch.bool, device=dev)  # (the kernel writes bytes 0 and 1)
+        d.cut, d.sad_min, d.hist_min = cut.data_ptr(), limits[0], limits[1]
+    lib = L.load()
+    ws = torch.empty((lib.dvie_synth_scene_ws_bytes(ctypes.byref(d)),), dtype=torch.uint8, device=dev)
+    d.sad, d.hdiff, d.ws = sad.data_ptr(), hdiff.data_ptr(), ws.data_ptr()
+    L.check(lib.dvie_synth_scene(ctypes.byref(d), L.stream_ptr(dev)), "synth scene")
+    return sad, hdiff, cut
+
+
+def scene_cuts(frames, mad, hist):
+    """Which neighbouring pairs of the uint8 device clips `frames` (B, T, H, W, 3) are scene cuts ->
+    a bool device tensor (B, T - 1): sad >= sad_min and hdiff >= hist_min with scene_stats' two sums
+    and scene_limits' two integers, compared in int64 by the statistic's finalize launch.  A pair's
+    flag depends on its two frames only."""
+    if frames.dim() != 5:
+        raise ValueError(f"frames: uint8 (B, T, H, W, 3), got {tuple(frames.shape)}")
+    return _scene_call(frames, scene_limits(frames.shape[2], frames.shape[3], mad, hist))[2]
+
+
+def cut_sources(levels):
+    """Which input frame fills the 2**levels - 1 slots between a flagged pair, in slot order: 0 the
+    left one, 1 the right one -- the nearest in time, the midpoint going to the left."""
+    if levels < 0:
+        raise ValueError(f"cut_sources: levels={levels} must not be negative")
+    step = 1 << levels
+    return [0 if j <= step // 2 else 1 for j in range(1, step)]
+
+
+def cut_fill(slots, cuts, levels):
+    """Hold frames across the flagged pairs, in place: `slots` uint8 (B, (T - 1) * 2**levels + 1,
+    ...) on the device, any strides over the two leading dimensions and the others contiguous
+    (frames, label maps or packed Y'CbCr frames; the transposed views interpolate returns are
+    taken as they are), `cuts` bool or uint8 (B, T - 1) on the device.  The slots between the two
+    inputs of a flagged pair become byte copies of the nearer input slot (cut_sources); nothing
+    else is written (dvie_synth_cutfill: one launch that reads the flags on the device).  -> slots"""
+    L.require_gpu(slots)
+    if slots.dtype != torch.uint8 or slots.dim() < 2:
+        raise ValueError(f"slots: uint8 (B, S, ...), got {tuple(slots.shape)} {slots.dtype}")
+    if cuts.dtype not in (torch.bool, torch.uint8) or cuts.dim() != 2 or cuts.device != slots.device:
+        raise ValueError(f"cuts: bool (B, T - 1) on {slots.device}, got {tuple(cuts.shape)} {cuts.dtype}")
+    B, S = slots.shape[:2]
+    T = cuts.shape[1] + 1
+    if levels < 0 or cuts.shape[0] != B or T < 2 or S != ((T - 1) << levels) + 1:
+        raise ValueError(f"cut_fill: {tuple(cuts.shape)} flags and levels={levels} need {B} clips of "
+                         f"{((T - 1) << max(levels, 0)) + 1} slots, got {tuple(slots.shape[:2])}")
+    tail = tuple(slots.shape[2:])
+    d = L.SynthCutFillDesc()
+    d.n0, _, d.s0, d.s1 = _lead_of(slots, tail, "slots")
+    d.n1, d.levels, d.nbytes = T, levels, 1
+    for n in tail:
+        d.nbytes *= n
+    if d.nbytes < 1:
+        raise ValueError(f"slots: empty dimensions in {tuple(slots.shape)}")
+    cuts = cuts.contiguous()
+    d.slots, d.cut = slots.data_ptr(), cuts.data_ptr()
+    L.check(L.load().dvie_synth_cutfill(ctypes.byref(d), L.stream_ptr(slots.device)), "synth cutfill")
+    return slots
+
+
+class SceneCuts:
+    """The two thresholds of scene-cut detection (interpolate(..., scene=)): a neighbouring pair of
+    input frames is a cut when its mean absolute luma difference is at least `mad` (0..255) AND its
+    32-bin luma histogram distance at least `hist` (0..1); scene_limits turns them into the integers
+    the device compares.  The defaults (30, 0.25) are provisional: they have not been validated on
+    real footage."""
+
+    def __init__(self, mad=30.0, hist=0.25):
+        if not 0 <= mad <= 255 or not 0 <= hist <= 1:
+            raise ValueError(f"SceneCuts: mad={mad} must be in 0..255 and hist={hist} in 0..1")
+        self.mad, self.hist = float(mad), float(hist)
+
+    def __repr__(self):
+        return f"SceneCuts(mad={self.mad}, hist={self.hist})"
+
+
 def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perceptual=None, msssim=None):
     """Score uint8 device frames `pred` (..., H, W, 3) against `gt` and, when both are given,
     label maps `pred_labels` (..., H, W) against `gt_labels` (dvie_synth_score: one fused pass
@@ -948,16 +1068,32 @@ class VideoSynthesizer:
                         k += m
         return fr, lb
 
-    def interpolate(self, frames, labels, levels=1):
+    def interpolate(self, frames, labels, levels=1, scene=None):
         """frames (B, T, H, W, 3), labels (B, T, H, W), uint8 on the device -> frames
         (B, (T - 1) * 2**levels + 1, H, W, 3) and labels of the same length (uint8, views of
         slot-major storage): the inputs unchanged at the multiples of 2**levels, between them
         the predictions of midpoint_schedule(T, levels).  A predicted frame enters the next
-        level as the network's raw fp32 output and with its argmax label."""
+        level as the network's raw fp32 output and with its argmax label.
+
+        scene: a SceneCuts -> (frames, labels, cuts): scene_cuts of the (H, W) input frames (never
+        of the padded canvas), the same rollout -- the forwards of a flagged pair run like every
+        other, so the batches, the captured graphs and the absence of host synchronisation are
+        what they are without it -- and then cut_fill of the frames and of the label maps: the
+        slots between a flagged pair are byte copies of the nearer input frame and label map, the
+        midpoint the left one's.  cuts: bool (B, T - 1) on the device.  None: two results, and
+        nothing of the above runs."""
         self._check(frames, labels)
         T = frames.shape[1]
         if T < 2 or levels < 0:
             raise ValueError("interpolate needs at least two frames and levels >= 0")
+        if scene is not None:
+            if not isinstance(scene, SceneCuts):
+                raise ValueError(f"scene: a SceneCuts or None, got {type(scene).__name__}")
+            cuts = scene_cuts(frames, scene.mad, scene.hist)
+            out_f, out_l = self.interpolate(frames, labels, levels)
+            cut_fill(out_f, cuts, levels)
+            cut_fill(out_l, cuts, levels)
+            return out_f, out_l, cuts
         sched = midpoint_schedule(T, levels)
         step = 1 << levels
         n_slots = (T - 1) * step + 1
@@ -966,7 +1102,7 @@ class VideoSynthesizer:
                             keep=lambda s: levels > 0 and s % 2 == 0)
         return fr.transpose(0, 1), lb.transpose(0, 1)
 
-    def interpolate_stream(self, chunks, levels=1):
+    def interpolate_stream(self, chunks, levels=1, scene=None):
         """interpolate() of a clip of any length in bounded memory: a generator over `chunks`, any
         iterable of (frames (B, t, H, W, 3), labels (B, t, H, W)) uint8 device tensors with t >= 1,
         the clip in order.  The last input frame of a chunk (its uint8 frame and label map) is
@@ -979,7 +1115,14 @@ class VideoSynthesizer:
         larger max_batch the windowing changes which pairs share a forward: `chunks`).  Nothing
         but the carried frame stays on the device between chunks (the plans and scratch of the
         synthesiser aside); what is yielded belongs to the consumer.  Fewer than two frames in
-        all: ValueError when the input ends."""
+        all: ValueError when the input ends.
+
+        scene: a SceneCuts -> (frames, labels, cuts) per window, interpolate(..., scene=) of carry +
+        chunk: cuts (B, t - 1) covers that window's pairs, the one after the carried frame
+        included, and the slots are filled before the carried frame's slot is dropped.  A pair's
+        flag depends on its two frames only, so the equalities above hold with the flags: the
+        streamed triples equal the per-window ones byte for byte, and with max_batch = 1 the
+        whole clip's."""
         carry, emitted, total = None, False, 0
         for frames, labels in chunks:
             self._check(frames, labels)
@@ -996,13 +1139,13 @@ class VideoSynthesizer:
             carry = (frames[:, -1:].clone(), labels[:, -1:].clone())
             if frames.shape[1] < 2:
                 continue  # (the first chunk was one frame: held)
-            out_f, out_l = self.interpolate(frames, labels, levels)
+            out_f, out_l, *cuts = self.interpolate(frames, labels, levels, scene)
             del frames, labels
             if emitted:
                 out_f, out_l = out_f[:, 1:], out_l[:, 1:]
             emitted = True
-            yield out_f, out_l
-            del out_f, out_l
+            yield (out_f, out_l, *cuts)
+            del out_f, out_l, cuts
         if total < 2:
             raise ValueError(f"interpolate_stream needs at least two frames, got {total}")
 

@@ -1138,6 +1138,73 @@ typedef struct dvie_synth_yuv_desc {
 int dvie_synth_yuv2rgb(const dvie_synth_yuv_desc* d, void* stream);
 int dvie_synth_rgb2yuv(const dvie_synth_yuv_desc* d, void* stream);
 
+/*
+ * dvie_synth_scene: the scene-cut statistic of every neighbouring frame pair of uint8 clips
+ * (synth.scene_stats / scene_cuts; DESIGN.md "Scene cuts").  Integer arithmetic only, so that every
+ * implementation agrees to the last bit.
+ *
+ * Frames: n0 clips of n1 frames, frame (i0, i1) at frames + i0*s0 + i1*s1 BYTES (strides may be
+ * anything, a transposed view of slot-major storage or a [:, ::2] view included); a frame is a
+ * contiguous h*w*3 block of uint8 RGB.  No alignment of frame bases is assumed.
+ *   Y        = (77*R + 150*G + 29*B + 128) >> 8 per pixel, in 0..255 (the weights sum to 256)
+ *   h_t[k]   = pixels of frame t with Y >> 3 == k, k < 32
+ * Outputs, indexed o = i0*(n1-1) + t for the pair (t, t+1), all written by the call (nothing is
+ * accumulated into, two calls give the same bits):
+ *   sad[o]   int64  sum over the h*w pixels of |Y_t - Y_{t+1}|, in 0 .. 255*h*w.  Width: a thread
+ *                   sums 8 differences <= 255 and a block 256 such threads (<= 522 240) in
+ *                   uint32; the per-pair sum over blocks is int64 (65536x65536: < 1.1e12).
+ *   hdiff[o] int64  sum over the 32 bins of |h_t[k] - h_{t+1}[k]|, in 0 .. 2*h*w.  Width: a block's
+ *                   bin count is <= 2048 in uint32; the per-frame bin sums over blocks are int64
+ *                   (<= h*w <= 2^32), and so is their difference and its sum over the bins.
+ *   cut[o]   uint8  (optional, may be NULL) sad[o] >= sad_min && hdiff[o] >= hist_min, compared in
+ *                   int64 by the finalize launch, 1 or 0.  sad_min and hist_min are read only then
+ *                   and must not be negative (synth.scene_limits makes them on the host).
+ * The pair's value depends on its two frames only.
+ * Launches: one pass in which every frame byte is read once (a block walks the frames of its
+ * 2048-pixel tile and keeps the previous frame's luma in registers), then a finalize launch that
+ * sums the per-block partials; no atomics on global memory, no host synchronisation.
+ * ws: dvie_synth_scene_ws_bytes(d) bytes = 4 * ceil(h*w / 2048) * (32*n0*n1 + n0*(n1-1)) rounded up
+ * to 8 (0 for a descriptor whose sizes are invalid), 8-byte aligned, fully overwritten.  sad and
+ * hdiff 8-byte aligned.  1 <= h, w <= 2^16, 1 <= n0 <= 65535, 2 <= n1 <= 65535.
+ */
+typedef struct dvie_synth_scene_desc {
+  const uint8_t* frames;
+  long long* sad;
+  long long* hdiff;
+  uint8_t* cut;
+  void* ws;
+  long long s0, s1;            /* byte strides of (i0, i1) */
+  long long sad_min, hist_min; /* read when cut is given */
+  int n0, n1, h, w;
+} dvie_synth_scene_desc;
+
+size_t dvie_synth_scene_ws_bytes(const dvie_synth_scene_desc* d);
+int dvie_synth_scene(const dvie_synth_scene_desc* d, void* stream);
+
+/*
+ * dvie_synth_cutfill: hold frames across the flagged pairs of interpolated clips, in place
+ * (synth.cut_fill).  n0 clips of (n1 - 1) * 2^levels + 1 slots, slot (b, s) the nbytes contiguous
+ * bytes at slots + b*s0 + s*s1 BYTES (any strides with |s1| >= nbytes: the transposed view of
+ * slot-major storage included); input frame t sits in slot t * 2^levels.  cut: the n0 x (n1 - 1)
+ * contiguous uint8 flags of dvie_synth_scene, on the device.  With step = 2^levels, for every pair
+ * (b, t) whose flag is not 0 and every 1 <= j < step:
+ *   slot t*step + j  <-  slot t*step        when j <= step/2  (the midpoint tie goes to the earlier frame)
+ *                    <-  slot (t+1)*step    otherwise
+ * byte for byte.  No byte of an unflagged pair, and no input slot, is written.  The unit is bytes,
+ * so the same call serves frames (h*w*3), label maps (h*w) and packed Y'CbCr frames.  16-byte moves
+ * when both slot bases are 16-byte aligned, bytewise otherwise.  One launch; levels = 0 launches
+ * nothing.  nbytes >= 1, 1 <= n0 <= 65535, n1 >= 2, 0 <= levels <= 8, (n1 - 1) * (2^levels - 1) <= 65535.
+ */
+typedef struct dvie_synth_cutfill_desc {
+  uint8_t* slots;
+  const uint8_t* cut;
+  long long s0, s1; /* byte strides of (clip, slot) */
+  long long nbytes; /* bytes of a slot */
+  int n0, n1, levels, pad0;
+} dvie_synth_cutfill_desc;
+
+int dvie_synth_cutfill(const dvie_synth_cutfill_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* The pairs of ops dvie_run_ops(ops, n) runs as chained launches (host only, nothing is
@@ -1153,7 +1220,8 @@ int dvie_ops_chain_pairs(const dvie_op* ops, int n, int* partner);
 
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
- * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim, synth_yuv). */
+ * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim, synth_yuv,
+ * synth_scene, synth_cutfill). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

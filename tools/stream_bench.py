@@ -13,6 +13,10 @@ the command logs.  The clip is smooth moving gradients with mild noise and block
 encoding time depends on the content: noise would be slower, flat frames faster).
 
     python tools/stream_bench.py [--frames 65] [--long-frames 257] [--window 16] [--rounds 3] [--json out.json]
+
+--synth_scd: only leg (c), with and without --synth_scd (default thresholds) in alternation, `--rounds`
+times: what detection and the fill launches cost the stream.  The clip has no cuts, so both legs
+write the same bytes.
 """
 import argparse
 import gc
@@ -80,7 +84,7 @@ def make_data(root, T, png):
             w.write(labels.reshape(T, -1))
 
 
-def run(run_dir, data, window, levels):
+def run(run_dir, data, window, levels, extra=()):
     """one `--split test` -> dict(wall_s, peak_bytes, stages: the numbers of the command's log line or None)"""
     out = os.path.join(data, "synth")
     shutil.rmtree(out, ignore_errors=True)
@@ -94,7 +98,7 @@ def run(run_dir, data, window, levels):
     t0 = time.perf_counter()
     M.main(["--split", "test", "--syn_type", "inter", "--input_h", str(H), "--input_w", str(W), "--precision", "bf16",
             "--bs", "8", "--load_dir", run_dir, "--checksession", "0", "--checkepoch", "1", "--checkpoint", "0",
-            "--cycgen_load_dir", data, "--synth_levels", str(levels), "--synth_window", str(window), "INTER",
+            "--cycgen_load_dir", data, "--synth_levels", str(levels), "--synth_window", str(window), *extra, "INTER",
             "--load_coarse"])
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
@@ -111,6 +115,29 @@ def run(run_dir, data, window, levels):
     return dict(wall_s=wall, peak_bytes=peak, stages=stages)
 
 
+def scd_legs(a, run_dir, data):
+    """y4m_window without and with --synth_scd, alternating -> median (min - max) wall time of both"""
+    legs = dict(scd_off=(), scd_on=("--synth_scd",))
+    slots = (a.frames - 1) * (1 << a.levels) + 1
+    run(run_dir, data, a.window, a.levels, ("--synth_scd",))  # warm-up: code objects, allocator
+    runs = {k: [] for k in legs}
+    for _ in range(a.rounds):
+        for k, extra in legs.items():
+            runs[k].append(run(run_dir, data, a.window, a.levels, extra))
+    res = {}
+    for k, v in runs.items():
+        walls = sorted(r["wall_s"] for r in v)
+        clip = sorted(r["stages"]["clip_s"] for r in v)
+        res[k] = dict(wall_s=walls[len(walls) // 2], wall_min_s=walls[0], wall_max_s=walls[-1],
+                      runs_wall_s=[r["wall_s"] for r in v], clip_s=clip[len(clip) // 2], clip_min_s=clip[0],
+                      clip_max_s=clip[-1], slots=slots, peak_mib=max(r["peak_bytes"] for r in v) / 2 ** 20)
+    res["config"] = dict(frames=a.frames, window=a.window, levels=a.levels, rounds=a.rounds, size=[H, W])
+    print(json.dumps(res, indent=1))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=65)
@@ -119,6 +146,7 @@ def main():
     ap.add_argument("--levels", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--synth_scd", action="store_true", help="only y4m_window, with and without --synth_scd")
     a = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="dvie_stream_bench_")
     try:
@@ -133,6 +161,8 @@ def main():
         dirs = {k: os.path.join(tmp, k) for k in ("png", "y4m", "y4m_long")}
         make_data(dirs["png"], a.frames, True)
         make_data(dirs["y4m"], a.frames, False)
+        if a.synth_scd:
+            return scd_legs(a, run_dir, dirs["y4m"])
         make_data(dirs["y4m_long"], a.long_frames, False)
         legs = dict(png_whole=(dirs["png"], 0), png_window=(dirs["png"], a.window), y4m_window=(dirs["y4m"], a.window))
         slots = (a.frames - 1) * (1 << a.levels) + 1

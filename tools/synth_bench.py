@@ -49,8 +49,16 @@
   repeat_interleave / avg_pool), rotating over buffer sets that exceed the Infinity Cache, the legs
   alternating, three rounds, the median and the spread, with the ratio composed / kernel.
 
+* scene cuts (--scene): us per call and TB/s of algorithmic bytes of synth.scene_stats (3 B per pixel
+  and frame), of synth.scene_cuts (the same pass, the flags written too) and of synth.cut_fill at
+  --synth_levels 2 over the frames of the interpolated clip (one flagged pair, and every pair
+  flagged: 2 x 3 slots per pair move), on one clip of 8 frames of 256x512 and on one 17-frame
+  1080p window, against the same statistic composed from torch ops on the device (integer luma,
+  abs difference and sum, index_add_ histogram), rotating over buffer sets that exceed the
+  Infinity Cache, the legs alternating, three rounds, the median and the spread.
+
     python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json]
-                                [--two-stage | --score | --pad | --vgg | --msssim | --yuv]
+                                [--two-stage | --score | --pad | --vgg | --msssim | --yuv | --scene]
 """
 import argparse
 import json
@@ -471,6 +479,62 @@ def yuv_numbers(dev, seconds):
     return out
 
 
+def composed_scene_stats(frames):
+    """scene_stats of uint8 (B, T, H, W, 3) with torch ops: what the kernel replaces (the same integers)"""
+    B, T = frames.shape[:2]
+    f = frames.to(torch.int32)
+    y = (77 * f[..., 0] + 150 * f[..., 1] + 29 * f[..., 2] + 128) >> 8
+    sad = (y[:, 1:] - y[:, :-1]).abs().sum((2, 3))
+    idx = ((y >> 3) + 32 * torch.arange(B * T, device=y.device, dtype=torch.int32).view(B, T, 1, 1)).reshape(-1)
+    h = torch.zeros((B * T * 32,), dtype=torch.int32, device=y.device).index_add_(0, idx, torch.ones_like(idx))
+    h = h.view(B, T, 32).long()
+    return sad, (h[:, 1:] - h[:, :-1]).abs().sum(-1)
+
+
+def scene_numbers(dev, seconds):
+    """scene_stats / scene_cuts / cut_fill against the torch composition of the statistic, alternating,
+    three rounds; buffer sets past the Infinity Cache"""
+    from deep_video_interpolation_extrapolation_amd.synth import cut_fill, scene_cuts, scene_stats
+    out = {}
+    levels = 2
+    for T, H, W in ((8, 256, 512), (17, 1080, 1920)):
+        clip_bytes = T * H * W * 3
+        sets = (320 << 20) // clip_bytes + 1
+        clips = [torch.randint(0, 256, (1, T, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(sets)]
+        a, b = scene_stats(clips[0]), composed_scene_stats(clips[0])
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+        S = ((T - 1) << levels) + 1
+        fsets = (320 << 20) // (S * H * W * 3) + 1
+        slots = [torch.randint(0, 256, (S, 1, H, W, 3), dtype=torch.uint8, device=dev).transpose(0, 1) for _ in range(fsets)]
+        one = torch.zeros((1, T - 1), dtype=torch.bool, device=dev)
+        one[0, (T - 1) // 2] = True
+        every = torch.ones((1, T - 1), dtype=torch.bool, device=dev)
+        k = [0, 0]
+
+        def rot(fn, which=0, n=sets):
+            def run():
+                i = k[which] = (k[which] + 1) % n
+                fn(i)
+            return run
+
+        legs = dict(stats=rot(lambda i: scene_stats(clips[i])),
+                    cuts=rot(lambda i: scene_cuts(clips[i], 30.0, 0.25)),
+                    stats_composed=rot(lambda i: composed_scene_stats(clips[i])),
+                    fill_one_cut=rot(lambda i: cut_fill(slots[i], one, levels), 1, fsets),
+                    fill_every_pair=rot(lambda i: cut_fill(slots[i], every, levels), 1, fsets))
+        rates = _alternate(legs, seconds)
+        moved = dict(stats=clip_bytes, cuts=clip_bytes, stats_composed=clip_bytes, fill_one_cut=2 * 3 * H * W * 3,
+                     fill_every_pair=2 * 3 * H * W * 3 * (T - 1))
+        row = {name: dict(us=1e6 / sorted(v)[1], runs_us=[1e6 / r for r in v], spread=(max(v) - min(v)) / sorted(v)[1],
+                          tbs=moved[name] * sorted(v)[1] / 1e12) for name, v in rates.items()}
+        row["buffer_sets"], row["fill_buffer_sets"] = sets, fsets
+        row["stats_composed_over_kernel"] = row["stats_composed"]["us"] / row["stats"]["us"]
+        out[f"1x{T}x{H}x{W}"] = row
+        del clips, slots
+        torch.cuda.empty_cache()
+    return out
+
+
 def pad_kernel_numbers(dev, seconds):
     """load_pad / finish_crop against load / finish on the same canvas, rotating over buffer sets of
     more than 2 GB in all (every launch streams from HBM).  GB/s are of algorithmic bytes: finish
@@ -648,7 +712,15 @@ def main():
     ap.add_argument("--vgg", action="store_true", help="only the perceptual-score legs")
     ap.add_argument("--msssim", action="store_true", help="only the multi-scale SSIM legs")
     ap.add_argument("--yuv", action="store_true", help="only the colour-conversion legs")
+    ap.add_argument("--scene", action="store_true", help="only the scene-cut legs")
     a = ap.parse_args()
+    if a.scene:
+        res = dict(scene=scene_numbers(torch.device("cuda:0"), a.seconds))
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.yuv:
         res = dict(yuv=yuv_numbers(torch.device("cuda:0"), a.seconds))
         print(json.dumps(res, indent=1))
