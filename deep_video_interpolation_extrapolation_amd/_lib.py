@@ -214,6 +214,19 @@ class SynthCutFillDesc(ctypes.Structure):
     ]
 
 
+TILE_MAX = 32  # DVIE_TILE_MAX: tiles per axis of dvie_synth_tile_blend
+
+
+class SynthTileBlendDesc(ctypes.Structure):
+    _fields_ = [
+        ("rgb_tiles", vp), ("seg_tiles", vp), ("rgb_out", vp), ("frame", vp), ("label", vp), ("label_canvas", vp),
+        ("n", i32), ("th", i32), ("tw", i32), ("hp", i32), ("wp", i32), ("h", i32), ("w", i32),
+        ("rgb_ld", i32), ("seg_ld", i32), ("n_classes", i32), ("overlap", i32),
+        ("nty", i32), ("ntx", i32), ("pad0", i32),
+        ("ys", i32 * TILE_MAX), ("xs", i32 * TILE_MAX),
+    ]
+
+
 class CosFeatDesc(ctypes.Structure):
     _fields_ = [
         ("feat", vp), ("ws", vp), ("out", vp), ("ld", i64),
@@ -330,7 +343,8 @@ _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, 
         104: SynthLoadDesc, 105: SynthFinishDesc, 106: SynthBridgeDesc, 107: SynthScoreDesc,
         108: SynthLoadPadDesc, 109: SynthFinishCropDesc, 110: SynthVggLoadDesc}
 # descriptors added after the set tests/test_perceptual_cpu.py pins for _ABI; load() checks both tables
-_ABI_MORE = {111: SynthMsssimDesc, 112: SynthYuvDesc, 113: SynthSceneDesc, 114: SynthCutFillDesc}
+_ABI_MORE = {111: SynthMsssimDesc, 112: SynthYuvDesc, 113: SynthSceneDesc, 114: SynthCutFillDesc,
+             115: SynthTileBlendDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -345,7 +359,7 @@ EXPORTS = [
     "dvie_synth_load_pad", "dvie_synth_finish_crop", "dvie_conv_zbits", "dvie_bn_partial_doubles",
     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks", "dvie_synth_msssim", "dvie_synth_msssim_ws_bytes",
     "dvie_synth_yuv2rgb", "dvie_synth_rgb2yuv", "dvie_conv_chain", "dvie_conv2d_chain", "dvie_ops_chain_pairs",
-    "dvie_synth_scene", "dvie_synth_scene_ws_bytes", "dvie_synth_cutfill",
+    "dvie_synth_scene", "dvie_synth_scene_ws_bytes", "dvie_synth_cutfill", "dvie_synth_tile_blend",
 ]
 
 _lib = None
@@ -383,7 +397,7 @@ def load():
                      "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
                      "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop",
                      "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_synth_msssim", "dvie_synth_yuv2rgb",
-                     "dvie_synth_rgb2yuv", "dvie_synth_scene", "dvie_synth_cutfill"):
+                     "dvie_synth_rgb2yuv", "dvie_synth_scene", "dvie_synth_cutfill", "dvie_synth_tile_blend"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]

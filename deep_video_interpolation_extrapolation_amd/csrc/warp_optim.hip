@@ -884,6 +884,7 @@ size_t dvie_abi_sizeof(int which) {
     case 112: return sizeof(dvie_synth_yuv_desc);
     case 113: return sizeof(dvie_synth_scene_desc);
     case 114: return sizeof(dvie_synth_cutfill_desc);
+    case 115: return sizeof(dvie_synth_tile_blend_desc);
     default: return 0;
   }
 }

@@ -55,6 +55,16 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
   --synth_scd_mad F         the mean absolute luma difference of a cut, 0..255 (default 30)
   --synth_scd_hist F        the histogram distance of a cut, 0..1 (default 0.25).  Both defaults are
                             provisional: they have not been validated on real footage
+  --synth_tile HxW          --split test (also with --synth_eval): frames whose canvas is larger than H x W
+                            are synthesised in overlapping tiles of that one size, blended on the device
+                            (synth.VideoSynthesizer(tile=), synth.tile_blend); H and W must be multiples
+                            of the net's coarsest stride (see --synth_pad).  Off by default.  One forward
+                            takes at most VideoSynthesizer.max_pixels pixels (4 793 489 for the bf16
+                            coarse net, half of that in fp32): a larger frame, 2160x3840 for one, needs
+                            this flag.  One log line per clip gives the tile grid
+  --synth_tile_overlap N    the least overlap of neighbouring tiles in pixels: a multiple of the net's
+                            coarsest stride, at most half the smaller tile side and at most 256 (default
+                            64, provisional: not validated on trained weights and real footage)
 """
 import argparse
 
@@ -67,6 +77,23 @@ def _window(text):
     if n == 1 or n < 0:
         raise argparse.ArgumentTypeError(f"--synth_window {n}: a window holds at least 2 input frames (0 = the whole clip)")
     return n
+
+
+def _tile(text):
+    """--synth_tile: HxW, two positive integers"""
+    import re
+    m = re.fullmatch(r"([1-9][0-9]*)x([1-9][0-9]*)", text)
+    if not m:
+        raise argparse.ArgumentTypeError(f"--synth_tile {text}: expected HxW, two positive integers (576x1024)")
+    return int(m.group(1)), int(m.group(2))
+
+
+def _overlap(text):
+    """--synth_tile_overlap: a non-negative integer"""
+    import re
+    if not re.fullmatch(r"[0-9]+", text):
+        raise argparse.ArgumentTypeError(f"--synth_tile_overlap {text}: expected a non-negative integer")
+    return int(text)
 
 
 def _unit_range(flag, hi):
@@ -137,6 +164,8 @@ GLOBAL = [
     ("--synth_scd", "synth_scd", bool, False, None),
     ("--synth_scd_mad", "synth_scd_mad", _unit_range("--synth_scd_mad", 255), 30.0, None),
     ("--synth_scd_hist", "synth_scd_hist", _unit_range("--synth_scd_hist", 1), 0.25, None),
+    ("--synth_tile", "synth_tile", _tile, None, None),
+    ("--synth_tile_overlap", "synth_tile_overlap", _overlap, 64, None),
 ]
 
 # second-stage flags of the reference's INTER sub-command (options/options.py:296-380);

@@ -349,20 +349,43 @@ class InterTrainer:
         return root
 
     def _synthesizer(self):
-        """--split test: the VideoSynthesizer of this run (--bs pairs per forward, --synth_pad)"""
+        """--split test: the VideoSynthesizer of this run (--bs pairs per forward, --synth_pad,
+        --synth_tile and --synth_tile_overlap; a tile that is no multiple of the net's stride is
+        the constructor's ValueError, which names that multiple)"""
         from ..synth import VideoSynthesizer
         pad = getattr(self.args, "synth_pad", "none")
         return VideoSynthesizer(self.model.module, max_batch=max(1, self.args.batch_size),
-                                pad=None if pad == "none" else pad)
+                                pad=None if pad == "none" else pad, tile=getattr(self.args, "synth_tile", None),
+                                overlap=getattr(self.args, "synth_tile_overlap", 64))
+
+    @staticmethod
+    def _size_hint(e):
+        """a FrameSizeError with the flag that runs the size: --synth_tile for a forward that is too
+        large, --synth_pad replicate for a size that is no multiple of the net's stride"""
+        from ..synth import FrameSizeError
+        hint = "--synth_tile HxW synthesises larger frames in tiles" if e.too_large else \
+            "--synth_pad replicate takes clips of any size"
+        out = FrameSizeError(f"{e} ({hint})")
+        out.too_large = e.too_large
+        return out
+
+    def _log_tiles(self, syn, clip, H, W):
+        """one line per clip when --synth_tile is given: the tile grid of its canvas and the overlap"""
+        if syn.tile is None:
+            return
+        ys, xs, th, tw = syn.tile_grid(H, W)
+        self.log.info("synth: {}: {}x{} frames in {} x {} tiles of {}x{}, overlap {}".format(
+            clip, H, W, len(ys), len(xs), th, tw, syn.overlap if len(ys) * len(xs) > 1 else 0))
 
     def _on_clip(self, fn, syn, frames, labels, *rest):
         """fn(syn, frames, labels, ...) of one clip; a frame size that --synth_pad none cannot run
         is reported with the flag that can"""
         from ..synth import FrameSizeError
         try:
+            self._log_tiles(syn, rest[0] if rest else "", frames.shape[2], frames.shape[3])
             return fn(syn, frames, labels, *rest)
         except FrameSizeError as e:
-            raise FrameSizeError(f"{e} (--synth_pad replicate takes clips of any size)") from None
+            raise self._size_hint(e) from None
 
     def _scene(self):
         """the synth.SceneCuts of --synth_scd (--synth_scd_mad, --synth_scd_hist), or None"""
@@ -528,6 +551,8 @@ class InterTrainer:
                 try:
                     for out_f, out_l, *cuts in syn.interpolate_stream(on_device, levels=levels, scene=scene):
                         S = out_f.shape[1]
+                        if g0 == 0:
+                            self._log_tiles(syn, src.name, out_f.shape[2], out_f.shape[3])
                         if src.kind == "png":
                             writer.put((g0, out_f[0].cpu().numpy(), out_l[0].cpu().numpy()))
                         else:
@@ -538,7 +563,7 @@ class InterTrainer:
                         g0 += S
                         del out_f, out_l, cuts
                 except FrameSizeError as e:
-                    raise FrameSizeError(f"{e} (--synth_pad replicate takes clips of any size)") from None
+                    raise self._size_hint(e) from None
                 torch.cuda.synchronize(self.device)
                 t_dev = time.perf_counter()
         finally:

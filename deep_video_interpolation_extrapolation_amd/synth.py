@@ -41,6 +41,14 @@ writes both canvases of an input slot (its last row and column repeated), and
 a later forward reads, the argmax over the whole canvas.  A prediction's pad region is the
 network's own output; the uint8 storage the caller gets stays (H, W).
 
+Frames larger than one forward (tile=(th, tw), opt-in): a canvas larger than the tile is cut into
+overlapping tiles of one shape (`tile_starts` per axis), the forward above runs per tile on crops of
+the input canvases, and `dvie_synth_tile_blend` cross-fades the tiles' raw images and coarse logits
+over the overlaps, writing the frame, the label, the label canvas and the kept fp32 form in one
+launch (`tile_blend`; include/dvie.h has the weights and the order of the sums).  `max_pixels` is
+the largest forward the conv kernels' 32-bit buffer range admits; a larger one is refused on the
+host (FrameSizeError) before anything is launched.
+
 Scoring: `frame_scores` (PSNR, SSIM, label agreement: dvie_synth_score) and, opt-in,
 `PerceptualScorer`, the per-frame VGG19 feature cosine: `dvie_synth_vgg_load` fills the input
 buffer of my_vgg's forward-only, arena-allocated scoring plan from the uint8 frames, and the
@@ -178,6 +186,75 @@ def synth_finish_crop(rgb, seg, frame, label, label_canvas=None, n_classes=20):
         assert label_canvas.dtype == torch.uint8 and label_canvas.is_contiguous() and label_canvas.shape == rgb.shape[:3]
         d.label_canvas = label_canvas.data_ptr()
     L.check(L.load().dvie_synth_finish_crop(ctypes.byref(d), L.stream_ptr(rgb.device)), "synth finish_crop")
+
+
+TILE_MAX = L.TILE_MAX  # tiles per axis
+TILE_MAX_OVERLAP = 256
+
+
+def tile_starts(size, tile, overlap, m):
+    """The tiles of one canvas axis -> (starts, extent).  size: the padded canvas size, a multiple of
+    m.  size <= tile: ([0], size), the axis is not tiled.  Otherwise n = ceil((size - overlap) /
+    (tile - overlap)) tiles of extent `tile` at starts[i] = (i * (size - tile) // (n - 1)) // m * m:
+    strictly increasing multiples of m from 0 to size - tile, neighbours overlapping by at least
+    `overlap`, at most three tiles over a coordinate.  tile % m == 0, overlap % m == 0, 0 <= overlap
+    <= min(tile // 2, 256), at most 32 tiles: ValueError naming the argument otherwise."""
+    for name, v in (("size", size), ("tile", tile), ("overlap", overlap), ("m", m)):
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise ValueError(f"tile_starts: {name}={v!r} must be an int")
+    if m < 1:
+        raise ValueError(f"tile_starts: m={m} must be at least 1")
+    if size < 1 or size % m:
+        raise ValueError(f"tile_starts: size={size} must be a positive multiple of m={m}")
+    if tile < 1 or tile % m:
+        raise ValueError(f"tile_starts: tile={tile} must be a positive multiple of m={m}")
+    if overlap < 0 or overlap % m or overlap > tile // 2 or overlap > TILE_MAX_OVERLAP:
+        raise ValueError(f"tile_starts: overlap={overlap} must be a multiple of m={m} in 0..min(tile // 2, "
+                         f"{TILE_MAX_OVERLAP}) = {min(tile // 2, TILE_MAX_OVERLAP)}")
+    if size <= tile:
+        return [0], size
+    n = -(-(size - overlap) // (tile - overlap))
+    if n > TILE_MAX:
+        raise ValueError(f"tile_starts: tile={tile} cuts size={size} into {n} tiles, at most {TILE_MAX} per axis")
+    return [(i * (size - tile) // (n - 1)) // m * m for i in range(n)], tile
+
+
+def tile_blend(rgb_tiles, seg_tiles, ys, xs, overlap, frame, label, rgb_out=None, label_canvas=None, n_classes=20):
+    """The tile outputs of one tiled forward -> the blended canvas (dvie_synth_tile_blend, one
+    launch).  rgb_tiles (nt, n, th, tw, rgb_ld) and seg_tiles (nt, n, th, tw, seg_ld): fp32,
+    contiguous, tile iy * len(xs) + ix at (ys[iy], xs[ix]) of the canvas (ys[-1] + th, xs[-1] + tw).
+    frame uint8 (n, h, w, 3) and label uint8 (n, h, w) get the top-left (h, w) of the blend (the
+    quantisation and the argmax of synth_finish); rgb_out, fp32 (n, hp, wp, rgb_ld), the blend in
+    channels 0-2 and zeros above; label_canvas, uint8 (n, hp, wp), the argmax of every canvas pixel.
+    include/dvie.h states the weights and the order of the sums."""
+    L.require_gpu(rgb_tiles)
+    ys, xs = list(ys), list(xs)
+    f32 = torch.float32
+    assert rgb_tiles.dtype == f32 and rgb_tiles.is_contiguous() and seg_tiles.dtype == f32 and seg_tiles.is_contiguous()
+    assert rgb_tiles.dim() == 5 and rgb_tiles.shape[:4] == seg_tiles.shape[:4], (rgb_tiles.shape, seg_tiles.shape)
+    nt, n, th, tw, rgb_ld = rgb_tiles.shape
+    if not 1 <= len(ys) <= TILE_MAX or not 1 <= len(xs) <= TILE_MAX or nt != len(ys) * len(xs):
+        raise ValueError(f"tile_blend: {len(ys)} x {len(xs)} starts (1..{TILE_MAX} per axis) for {nt} tiles")
+    hp, wp = ys[-1] + th, xs[-1] + tw
+    assert frame.dtype == torch.uint8 and frame.is_contiguous() and label.dtype == torch.uint8 and label.is_contiguous()
+    assert frame.dim() == 4 and frame.shape[0] == n and frame.shape[3] == 3 and label.shape == frame.shape[:3]
+    d = L.SynthTileBlendDesc()
+    d.rgb_tiles, d.seg_tiles, d.frame, d.label = rgb_tiles.data_ptr(), seg_tiles.data_ptr(), frame.data_ptr(), label.data_ptr()
+    d.n, d.th, d.tw, d.hp, d.wp = n, th, tw, hp, wp
+    d.h, d.w = frame.shape[1:3]
+    d.rgb_ld, d.seg_ld, d.n_classes, d.overlap = rgb_ld, seg_tiles.shape[4], n_classes, overlap
+    d.nty, d.ntx = len(ys), len(xs)
+    for k, v in enumerate(ys):
+        d.ys[k] = v
+    for k, v in enumerate(xs):
+        d.xs[k] = v
+    if rgb_out is not None:
+        assert rgb_out.dtype == f32 and rgb_out.is_contiguous() and tuple(rgb_out.shape) == (n, hp, wp, rgb_ld), rgb_out.shape
+        d.rgb_out = rgb_out.data_ptr()
+    if label_canvas is not None:
+        assert label_canvas.dtype == torch.uint8 and label_canvas.is_contiguous() and tuple(label_canvas.shape) == (n, hp, wp)
+        d.label_canvas = label_canvas.data_ptr()
+    L.check(L.load().dvie_synth_tile_blend(ctypes.byref(d), L.stream_ptr(rgb_tiles.device)), "synth tile_blend")
 
 
 class FrameScores:
@@ -803,7 +880,9 @@ class SynthScores:
 
 
 class FrameSizeError(ValueError):
-    """a frame size that VideoSynthesizer(pad=None) cannot run"""
+    """a frame size that VideoSynthesizer cannot run: no multiple of the net's stride with pad=None,
+    or (too_large) a forward of more than max_pixels pixels, which tile= cuts into smaller ones"""
+    too_large = False
 
 
 class _Captured:
@@ -860,9 +939,20 @@ class VideoSynthesizer:
     persists through the rollout: a prediction is the network's raw output over the whole canvas,
     its label canvas the argmax over the whole canvas, and both feed later forwards as they are
     (the pad region is not re-replicated).  What is returned is cropped to (H, W), so the result
-    equals padding the uint8 inputs, running pad=None on the canvas and cropping."""
+    equals padding the uint8 inputs, running pad=None on the canvas and cropping.
+    tile: None -- every forward covers the whole canvas; (th, tw), multiples of `multiple` -- a
+    canvas larger than that in either direction is cut into overlapping tiles of one shape
+    (tile_starts per axis, `tiles`), every forward runs on one tile of the chunk's pairs, and
+    tile_blend cross-fades the tiles' raw images and coarse logits over the overlaps into the
+    frame, the label and the kept fp32 form (the crop of a padded canvas included).  overlap: the
+    least number of rows / columns neighbouring tiles share, a multiple of `multiple` in
+    0..min(th, tw) // 2 and at most 256 (64 is provisional: unvalidated on trained weights).  A
+    canvas that fits one tile runs exactly as with tile=None.  A tiled frame approximates the
+    untiled one: the net's receptive field is wider than any overlap, and a tile's inner borders
+    see zero padding.  A forward of more than `max_pixels` pixels raises FrameSizeError before
+    anything is launched."""
 
-    def __init__(self, net, max_batch=8, graph=False, pad=None):
+    def __init__(self, net, max_batch=8, graph=False, pad=None, tile=None, overlap=64):
         from .nets.ExtraNet import ExtraNet, ExtraRefineNet, ExtraStage3Net
         from .nets.HRNet import HRNet
         from .nets.InterNet import InterNet
@@ -890,13 +980,23 @@ class VideoSynthesizer:
         self.net, self.cm, self.max_batch, self.graph = net, cm, int(max_batch), bool(graph)
         self._scratch = {}  # (n, H, W, device) -> the scratch tensors of a forward
         self._graphs = {}
+        self._tile_scratch = {}  # (n, th, tw, tiles, device) -> the tile inputs and the stash of a tiled forward
+        self._max_pixels = None
+        self.tile, self.overlap = None, 0
+        if tile is not None:
+            m = self.multiple
+            if not isinstance(tile, (tuple, list)) or len(tile) != 2 or \
+                    any(not isinstance(v, int) or isinstance(v, bool) or v < m or v % m for v in tile):
+                raise ValueError(f"tile must be None or (th, tw), positive multiples of the net's multiple {m}, got {tile!r}")
+            tile_starts(min(tile), min(tile), overlap, m)  # (the overlap rules, for the smaller side)
+            self.tile, self.overlap = (int(tile[0]), int(tile[1])), int(overlap)
 
     def reset(self):
         """drop the captured graphs and scratch (after net.to(...) or a load that re-allocates)"""
         for c in self._graphs.values():
             for p in c.plans:
                 p.busy = False
-        self._graphs, self._scratch = {}, {}
+        self._graphs, self._scratch, self._tile_scratch = {}, {}, {}
 
     @property
     def multiple(self):
@@ -908,6 +1008,62 @@ class VideoSynthesizer:
         """(Hp, Wp) of the canvas an (H, W) frame is synthesised on when pad is "replicate": both
         rounded up to `multiple`"""
         return canvas_size(H, W, self.multiple)
+
+    def tile_grid(self, H, W):
+        """(ys, xs, th, tw): the tile starts per axis of the canvas of an (H, W) frame and the one
+        shape of its tiles; ([0], [0], Hp, Wp) without tile= or when the canvas fits one tile"""
+        Hp, Wp = self.canvas(H, W) if self.pad else (H, W)
+        if self.tile is None:
+            return [0], [0], Hp, Wp
+        m = self.multiple
+        ys, th = tile_starts(Hp, self.tile[0], self.overlap, m)
+        xs, tw = tile_starts(Wp, self.tile[1], self.overlap, m)
+        return ys, xs, th, tw
+
+    def tiles(self, H, W):
+        """the tiles [(y0, x0, th, tw)] of the canvas of an (H, W) frame in row-major order: one
+        shape for all of them (one plan serves them); one tile, the canvas, when it fits"""
+        ys, xs, th, tw = self.tile_grid(H, W)
+        return [(y0, x0, th, tw) for y0 in ys for x0 in xs]
+
+    RANGE_BYTES = 0xFFFFFF00  # the conv kernels address one image of a map through a 32-bit buffer range
+
+    @property
+    def max_pixels(self):
+        """The largest Hp * Wp of one forward: one image of the widest activation of the net's
+        plans, at the net's precision, must stay below RANGE_BYTES (dvie_conv2d_fwd's rule).  The
+        widths come from a dry lowering of every stage at a small size: per buffer its bytes per
+        pixel of the full-resolution frame.  HRNet's stacked head buffer is not counted: the
+        lowering splits it in two where it would exceed the range (HRNet._heads)."""
+        if self._max_pixels is None:
+            from fractions import Fraction
+            m = self.multiple * 4
+            graphs = [self.cm._lower(E.Graph(self.cm.dtype), m, m, dry=True, labels=True)]
+            for st in self.stages:
+                g = E.Graph(st.dtype)
+                st._lower(g, m, m, False, True)
+                graphs.append(g)
+            widest = Fraction(0)
+            for g in graphs:
+                for b in g.buffers:
+                    if b.name == "heads_hidden":
+                        continue
+                    es = 2 if (b.dtype or g.dtype) == torch.bfloat16 else 4
+                    widest = max(widest, Fraction(b.H * b.W * b.C * es, m * m))
+            self._max_pixels = int((self.RANGE_BYTES - 1) / widest)
+        return self._max_pixels
+
+    def _check_size(self, H, W):
+        """FrameSizeError (too_large) when a forward of an (H, W) frame -- its tile, or the whole
+        canvas -- has more than max_pixels pixels"""
+        _, _, th, tw = self.tile_grid(H, W)
+        if th * tw > self.max_pixels:
+            what = f"a tile of {th}x{tw}" if self.tile is not None else f"the {th}x{tw} canvas of a {H}x{W} frame"
+            e = FrameSizeError(f"{what} is a forward of {th * tw} pixels, more than max_pixels = {self.max_pixels} (one "
+                               f"image of the net's widest activation must stay below {self.RANGE_BYTES:#x} bytes): pass "
+                               f"tile=(th, tw) with th * tw <= {self.max_pixels} to synthesise the frame in tiles")
+            e.too_large = True
+            raise e
 
     # ---------------- one forward ----------------
     def _plans(self, n, H, W, dev):
@@ -959,12 +1115,55 @@ class VideoSynthesizer:
                 plan.set_input_labels("nseg", [la, lb])
                 plan.set_output_nchw("out", imgs[k + 1].permute(0, 3, 1, 2))
             plan.run_forward()
+        if frame is None:  # (a tile of a tiled forward: tile_blend finishes the canvas)
+            return
         if frame.shape[1:3] == (H, W):
             synth_finish(rgb, seg, frame, label, n_classes=self.cm.n_classes)
         else:
             synth_finish_crop(rgb, seg, frame, label, lcan, n_classes=self.cm.n_classes)
 
-    def _pair(self, xa, xb, la, lb, rgb, frame, label, lcan=None):
+    def _tile_scratch_of(self, n, th, tw, nt, dev):
+        """the reused scratch of a tiled forward of n pairs: the tile crops of the four inputs, the
+        stash of every tile's raw rgb and coarse logits and, for graph replay, the tile's unused
+        uint8 outputs"""
+        key = (n, th, tw, nt, dev)
+        if key not in self._tile_scratch:
+            f32, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
+            sc = {"xa": torch.empty((n, th, tw, 8), **f32), "xb": torch.empty((n, th, tw, 8), **f32),
+                  "la": torch.empty((n, th, tw), **u8), "lb": torch.empty((n, th, tw), **u8),
+                  "rgb": torch.empty((nt, n, th, tw, 8), **f32),
+                  "seg": torch.empty((nt, n, th, tw, E.rup(self.cm.seg_out_dim, 8)), **f32)}
+            if self.graph:
+                sc["frame"], sc["label"] = torch.empty((n, th, tw, 3), **u8), torch.empty((n, th, tw), **u8)
+            self._tile_scratch[key] = sc
+        return self._tile_scratch[key]
+
+    def _pair(self, xa, xb, la, lb, rgb, frame, label, lcan=None, keep=True):
+        """one forward of n pairs over the canvas of `rgb`; keep: a later forward reads rgb (a
+        tiled forward writes it only then)"""
+        n, H, W, _ = rgb.shape
+        if self.tile is not None and (H > self.tile[0] or W > self.tile[1]):
+            return self._pair_tiled(xa, xb, la, lb, rgb, frame, label, lcan, keep)
+        return self._pair_whole(xa, xb, la, lb, rgb, frame, label, lcan)
+
+    def _pair_tiled(self, xa, xb, la, lb, rgb, frame, label, lcan, keep):
+        """the forward per tile on crops of the input canvases, every tile's raw rgb and coarse
+        logits collected in the stash, then one tile_blend over the canvas"""
+        n, H, W, _ = rgb.shape
+        ys, xs, th, tw = self.tile_grid(H, W)  # ((H, W) is the canvas: its own canvas)
+        sc = self._tile_scratch_of(n, th, tw, len(ys) * len(xs), rgb.device)
+        t = 0
+        for y0 in ys:
+            for x0 in xs:
+                for dst, src in ((sc["xa"], xa), (sc["xb"], xb), (sc["la"], la), (sc["lb"], lb)):
+                    dst.copy_(src[:, y0:y0 + th, x0:x0 + tw])
+                self._pair_whole(sc["xa"], sc["xb"], sc["la"], sc["lb"], sc["rgb"][t], sc.get("frame"), sc.get("label"))
+                sc["seg"][t].copy_(self._scratch_of(n, th, tw, rgb.device)["seg"])
+                t += 1
+        tile_blend(sc["rgb"], sc["seg"], ys, xs, self.overlap, frame, label, rgb if keep else None, lcan,
+                   n_classes=self.cm.n_classes)
+
+    def _pair_whole(self, xa, xb, la, lb, rgb, frame, label, lcan=None):
         n, H, W, _ = rgb.shape
         if not self.graph:
             return self._run(self._plans(n, H, W, rgb.device), xa, xb, la, lb, rgb, frame, label, lcan)
@@ -986,6 +1185,7 @@ class VideoSynthesizer:
             raise FrameSizeError(f"H and W must be multiples of {m}, got {tuple(frames.shape[2:4])}")
         if frames.shape[2] < 1 or frames.shape[3] < 1:
             raise ValueError(f"H and W must be at least 1, got {tuple(frames.shape[2:4])}")
+        self._check_size(frames.shape[2], frames.shape[3])
 
     def chunks(self, triples, B):
         """The forwards of one level: its pairs (triple, clip), triples in order and the clips
@@ -1042,7 +1242,7 @@ class VideoSynthesizer:
                         a, b, o, b0, b1 = chunk[0]
                         rgb = res[o][b0:b1] if o in res else tmp[:b1 - b0]
                         self._pair(res[a][b0:b1], res[b][b0:b1], lc[a][b0:b1], lc[b][b0:b1], rgb, fr[o, b0:b1],
-                                   lb[o, b0:b1], lc[o][b0:b1] if padded and o in res else None)
+                                   lb[o, b0:b1], lc[o][b0:b1] if padded and o in res else None, keep=o in res)
                         continue
                     # several triples: gather their frames, run one forward, scatter its outputs
                     n = sum(b1 - b0 for *_, b0, b1 in chunk)
@@ -1055,7 +1255,8 @@ class VideoSynthesizer:
                     la = torch.cat([lc[a][b0:b1] for a, _, _, b0, b1 in chunk])
                     lb2 = torch.cat([lc[b][b0:b1] for _, b, _, b0, b1 in chunk])
                     kept = padded and any(o in res for _, _, o, _, _ in chunk)
-                    self._pair(xa, xb, la, lb2, tmp[:n], tfr[:n], tlb[:n], tlc[:n] if kept else None)
+                    self._pair(xa, xb, la, lb2, tmp[:n], tfr[:n], tlb[:n], tlc[:n] if kept else None,
+                               keep=any(o in res for _, _, o, _, _ in chunk))
                     k = 0
                     for _, _, o, b0, b1 in chunk:
                         m = b1 - b0

@@ -1205,6 +1205,54 @@ typedef struct dvie_synth_cutfill_desc {
 
 int dvie_synth_cutfill(const dvie_synth_cutfill_desc* d, void* stream);
 
+/*
+ * dvie_synth_tile_blend: the tile outputs of one tiled forward -> the frame, the label map and the
+ * kept fp32 form of a canvas (synth.tile_blend; DESIGN.md "Tiled synthesis").  One launch.
+ *
+ * The canvas (hp, wp) is covered by nty x ntx tiles of one shape (th, tw): tile t = iy*ntx + ix has
+ * its top-left at (ys[iy], xs[ix]).  rgb_tiles (nt, n, th, tw, rgb_ld) and seg_tiles
+ * (nt, n, th, tw, seg_ld) are fp32, contiguous and 16-byte aligned: every tile's raw image and
+ * logits of the n images of the forward.
+ *
+ * Weight of tile t at canvas pixel (y, x): wy * wx, with per axis (start s, extent e, size S,
+ * coordinate c)
+ *   a = s > 0     ? c - s + 1 : overlap + 1
+ *   b = s + e < S ? s + e - c : overlap + 1
+ *   w = min(a, b, overlap + 1)
+ * an integer in 1 .. 257 (a canvas border does not ramp; overlap = 0: every weight is 1).
+ * Value of a pixel and channel, over its covering tiles in ascending t:
+ *   one tile:  the tile's value, bit for bit
+ *   several:   acc = 0.f; acc = acc + (float)w_t * v_t per tile (the multiply and the add rounded
+ *              separately, no fma); then acc / (float)(sum of w_t), correctly rounded.
+ * Outputs (every byte has one owning lane; no atomics, nothing is read back):
+ *   rgb_out      fp32 (n, hp, wp, rgb_ld), optional: channels 0-2 the blend, 3 and up zero
+ *   frame        uint8 (n, h, w, 3): the top-left (h, w) of the blend through dvie_synth_finish's
+ *                quantisation
+ *   label        uint8 (n, h, w): dvie_synth_finish's argmax (lowest index on ties) of the blended
+ *                logits of the first n_classes classes
+ *   label_canvas uint8 (n, hp, wp), optional: the same argmax over every canvas pixel
+ * No blended logit map is written.  EINVAL before any launch: null pointers, leading dimensions
+ * that are no multiple of 4 (rgb_ld >= 4), unaligned tiles or rgb_out, nty / ntx outside 1..32,
+ * starts that do not increase, a tile that leaves the canvas, tiles that do not cover it (the first
+ * start is 0, neighbours leave no gap, the last tile ends at the canvas edge), h > hp or w > wp,
+ * n_classes outside 1..min(seg_ld, 256), overlap outside 0..256.  All offsets are 64-bit.
+ */
+#define DVIE_TILE_MAX 32
+typedef struct dvie_synth_tile_blend_desc {
+  const float* rgb_tiles;
+  const float* seg_tiles;
+  float* rgb_out; /* may be NULL */
+  uint8_t* frame;
+  uint8_t* label;
+  uint8_t* label_canvas; /* may be NULL */
+  int n, th, tw, hp, wp, h, w;
+  int rgb_ld, seg_ld, n_classes, overlap;
+  int nty, ntx, pad0;
+  int ys[DVIE_TILE_MAX], xs[DVIE_TILE_MAX];
+} dvie_synth_tile_blend_desc;
+
+int dvie_synth_tile_blend(const dvie_synth_tile_blend_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* The pairs of ops dvie_run_ops(ops, n) runs as chained launches (host only, nothing is
@@ -1221,7 +1269,7 @@ int dvie_ops_chain_pairs(const dvie_op* ops, int n, int* partner);
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
  * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim, synth_yuv,
- * synth_scene, synth_cutfill). */
+ * synth_scene, synth_cutfill, synth_tile_blend). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

@@ -57,8 +57,19 @@
   abs difference and sum, index_add_ histogram), rotating over buffer sets that exceed the
   Infinity Cache, the legs alternating, three rounds, the median and the spread.
 
+* tiled synthesis (--tile): us per call and TB/s of algorithmic bytes (every tile element read once,
+  the outputs written) of synth.tile_blend for one 2160x3840 canvas from 4 tiles of 1152x2048 at
+  overlap 64, 20 classes, with every output and with the frame and label only, against the same blend
+  composed from torch ops on the device (weights precomputed), rotating over two buffer sets of
+  1.5 GB each, the legs alternating, three rounds, the median and the spread; one forward of a bf16
+  coarse InterNet (random weights) at 1080x1920 untiled against tile=(576, 1024), ms per forward
+  alternating and max_memory_allocated of each alone; 2160x3840 tiled (1152x2048): frames/s and peak
+  memory, with the host guard's refusal of the untiled form recorded (nothing of it is launched);
+  and PSNR / mean absolute difference of the tiled against the untiled uint8 frame at 1080x1920,
+  inside and outside the overlap bands (information only).
+
     python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json]
-                                [--two-stage | --score | --pad | --vgg | --msssim | --yuv | --scene]
+                                [--two-stage | --score | --pad | --vgg | --msssim | --yuv | --scene | --tile]
 """
 import argparse
 import json
@@ -535,6 +546,167 @@ def scene_numbers(dev, seconds):
     return out
 
 
+def make_inter_net():
+    a = types.SimpleNamespace(syn_type="inter", highres_large=False, coarse_model="HRNet", precision="bf16")
+    torch.manual_seed(1024)
+    return nets.InterNet(a)
+
+
+def _tile_weights(ys, xs, th, tw, ov, dev):
+    """fp32 (nt, th, tw): the blend weight of every tile over its own pixels, and (hp, wp) their sum"""
+    def axis(s, e, S):
+        c = torch.arange(s, s + e, device=dev)
+        a = c - s + 1 if s > 0 else torch.full_like(c, ov + 1)
+        b = s + e - c if s + e < S else torch.full_like(c, ov + 1)
+        return torch.minimum(torch.minimum(a, b), torch.full_like(c, ov + 1)).float()
+    hp, wp = ys[-1] + th, xs[-1] + tw
+    w = torch.stack([axis(y, th, hp)[:, None] * axis(x, tw, wp)[None, :] for y in ys for x in xs])
+    total = torch.zeros((hp, wp), device=dev)
+    for t, (y, x) in enumerate((y, x) for y in ys for x in xs):
+        total[y:y + th, x:x + tw] += w[t]
+    return w, total
+
+
+def composed_tile_blend(rgb_tiles, seg_tiles, ys, xs, w, total, frame, label, rgb_out, lcan):
+    """the blend with torch ops on the device: what the kernel replaces (every pixel goes through
+    w * v / w, so single-covered pixels are not bit-equal; timing only)"""
+    nt, n, th, tw, _ = rgb_tiles.shape
+    hp, wp = total.shape
+    acc = torch.zeros((n, hp, wp, 3), device=rgb_tiles.device)
+    seg = torch.zeros((n, hp, wp, 20), device=rgb_tiles.device)
+    for t, (y, x) in enumerate((y, x) for y in ys for x in xs):
+        acc[:, y:y + th, x:x + tw] += w[t][None, :, :, None] * rgb_tiles[t][..., :3]
+        seg[:, y:y + th, x:x + tw] += w[t][None, :, :, None] * seg_tiles[t][..., :20]
+    acc /= total[None, :, :, None]
+    seg /= total[None, :, :, None]
+    frame.copy_((acc.clamp(-1, 1) * 127.5 + 127.5).round_())
+    lab = seg.argmax(-1)
+    label.copy_(lab)
+    if lcan is not None:
+        lcan.copy_(lab)
+    if rgb_out is not None:
+        rgb_out[..., :3] = acc
+        rgb_out[..., 3:] = 0
+
+
+def tile_blend_numbers(dev, seconds):
+    from deep_video_interpolation_extrapolation_amd.synth import tile_blend, tile_starts
+    hp, wp, th, tw, ov, n = 2160, 3840, 1152, 2048, 64, 1
+    ys, xs = tile_starts(hp, th, ov, 4)[0], tile_starts(wp, tw, ov, 4)[0]
+    nt, sets = len(ys) * len(xs), 2
+    rgb = [torch.rand((nt, n, th, tw, 8), device=dev) * 2.4 - 1.2 for _ in range(sets)]
+    seg = [torch.randn((nt, n, th, tw, 24), device=dev) for _ in range(sets)]
+    u8 = dict(dtype=torch.uint8, device=dev)
+    frame = [torch.empty((n, hp, wp, 3), **u8) for _ in range(sets)]
+    label = [torch.empty((n, hp, wp), **u8) for _ in range(sets)]
+    lcan = [torch.empty((n, hp, wp), **u8) for _ in range(sets)]
+    out = [torch.empty((n, hp, wp, 8), device=dev) for _ in range(sets)]
+    w, total = _tile_weights(ys, xs, th, tw, ov, dev)
+    k = [0]
+
+    def rot(fn):
+        def run():
+            i = k[0] = (k[0] + 1) % sets
+            fn(i)
+        return run
+
+    legs = dict(blend_all_outputs=rot(lambda i: tile_blend(rgb[i], seg[i], ys, xs, ov, frame[i], label[i], out[i], lcan[i])),
+                blend_frame_label=rot(lambda i: tile_blend(rgb[i], seg[i], ys, xs, ov, frame[i], label[i])),
+                composed_all_outputs=rot(lambda i: composed_tile_blend(rgb[i], seg[i], ys, xs, w, total, frame[i], label[i],
+                                                                       out[i], lcan[i])))
+    # the two forms agree up to the rounding of w * v / w
+    tile_blend(rgb[0], seg[0], ys, xs, ov, frame[0], label[0], out[0], lcan[0])
+    composed_tile_blend(rgb[0], seg[0], ys, xs, w, total, frame[1], label[1], out[1], lcan[1])
+    agree = dict(frame_bytes_differing=int((frame[0] != frame[1]).sum()), labels_differing=int((label[0] != label[1]).sum()),
+                 max_abs_rgb=float((out[0] - out[1]).abs().max()))
+    cpix, tbytes = n * hp * wp, nt * n * th * tw * 128
+    nbytes = dict(blend_all_outputs=tbytes + cpix * (32 + 3 + 1 + 1), blend_frame_label=tbytes + cpix * 4,
+                  composed_all_outputs=tbytes + cpix * (32 + 3 + 1 + 1))
+    rates = _alternate(legs, seconds)
+    row = {name: dict(us=1e6 / sorted(v)[1], runs_us=[1e6 / r for r in v], spread=(max(v) - min(v)) / sorted(v)[1],
+                      tbs=nbytes[name] * sorted(v)[1] / 1e12, algorithmic_bytes=nbytes[name]) for name, v in rates.items()}
+    row["buffer_sets"], row["tiles"], row["agreement_with_composed"] = sets, [ys, xs, th, tw], agree
+    row["composed_over_kernel"] = row["composed_all_outputs"]["us"] / row["blend_all_outputs"]["us"]
+    return row
+
+
+def _peak_of(net, make, run, dev):
+    """max_memory_allocated of run(make()) alone (two calls), the net's plans dropped before and after;
+    before_gib: what was allocated when it began (the weights, the clip, whatever else is alive)"""
+    import gc
+    net.coarse_model._pool.clear()
+    net.coarse_model.last_plan = None
+    gc.collect()
+    torch.cuda.empty_cache()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    syn = make()
+    run(syn)
+    run(syn)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated(dev)
+    del syn
+    net.coarse_model._pool.clear()
+    net.coarse_model.last_plan = None
+    gc.collect()
+    torch.cuda.empty_cache()
+    return dict(peak_gib=peak / 2 ** 30, before_gib=base / 2 ** 30, peak_over_before_gib=(peak - base) / 2 ** 30)
+
+
+def tile_forward_numbers(dev, seconds):
+    from deep_video_interpolation_extrapolation_amd.synth import FrameSizeError
+    net = make_inter_net().to(dev).eval()
+    out = {}
+    # ---- 1080x1920: one forward untiled against 4 tiles of 576x1024 ----
+    H, W = 1080, 1920
+    frames = torch.randint(0, 256, (1, 2, H, W, 3), dtype=torch.uint8, device=dev)
+    labels = torch.randint(0, 20, (1, 2, H, W), dtype=torch.uint8, device=dev)
+    make = dict(untiled=lambda: VideoSynthesizer(net, max_batch=1), tiled=lambda: VideoSynthesizer(net, max_batch=1,
+                                                                                                   tile=(576, 1024)))
+    run = lambda syn: syn.interpolate(frames, labels, 1)  # noqa: E731
+    row = {name: _peak_of(net, mk, run, dev) for name, mk in make.items()}
+    syns = {name: mk() for name, mk in make.items()}
+    rates = _alternate({name: (lambda s=s: run(s)) for name, s in syns.items()}, seconds)
+    for name, v in rates.items():
+        row[name].update(ms_per_forward=1e3 / sorted(v)[1], runs_ms=[1e3 / r for r in v], spread=(max(v) - min(v)) / sorted(v)[1])
+    row["tiles"] = syns["tiled"].tiles(H, W)
+    row["tiled_over_untiled"] = row["tiled"]["ms_per_forward"] / row["untiled"]["ms_per_forward"]
+    # the difference tiling makes (random weights): the synthesised frame, inside and outside the overlap bands
+    a, b = run(syns["untiled"])[0][0, 1].float(), run(syns["tiled"])[0][0, 1].float()
+    ys, xs, th, tw = syns["tiled"].tile_grid(H, W)
+    cover = torch.zeros((H, W), device=dev)
+    for y in ys:
+        for x in xs:
+            cover[y:y + th, x:x + tw] += 1
+    diff = {}
+    for name, m in (("overlap_bands", cover > 1), ("outside", cover == 1), ("all", cover >= 1)):
+        d = (a - b)[m]
+        mse = float((d * d).mean())
+        diff[name] = dict(pixels=int(m.sum()), mean_abs=float(d.abs().mean()),
+                          psnr=float("inf") if mse == 0 else 10 * torch.log10(torch.tensor(255.0 ** 2 / mse)).item())
+    row["tiled_vs_untiled_frame"] = dict(weights="random (seed 1024)", **diff)
+    out["1x1080x1920_bf16"] = row
+    del syns, a, b
+    # ---- 2160x3840: tiled only; the untiled form is refused on the host ----
+    H, W = 2160, 3840
+    frames = torch.randint(0, 256, (1, 2, H, W, 3), dtype=torch.uint8, device=dev)
+    labels = torch.randint(0, 20, (1, 2, H, W), dtype=torch.uint8, device=dev)
+    try:
+        VideoSynthesizer(net, max_batch=1)._check_size(H, W)
+        refusal = None
+    except FrameSizeError as e:
+        refusal = str(e)
+    mk = lambda: VideoSynthesizer(net, max_batch=1, tile=(1152, 2048))  # noqa: E731
+    row = _peak_of(net, mk, run, dev)
+    syn = mk()
+    v = _alternate(dict(tiled=lambda: run(syn)), seconds)["tiled"]
+    row.update(frames_per_s=sorted(v)[1], runs=v, spread=(max(v) - min(v)) / sorted(v)[1], tiles=syn.tiles(H, W),
+               max_pixels=syn.max_pixels, untiled_refusal=refusal)
+    out["1x2160x3840_bf16"] = row
+    return out
+
+
 def pad_kernel_numbers(dev, seconds):
     """load_pad / finish_crop against load / finish on the same canvas, rotating over buffer sets of
     more than 2 GB in all (every launch streams from HBM).  GB/s are of algorithmic bytes: finish
@@ -713,7 +885,18 @@ def main():
     ap.add_argument("--msssim", action="store_true", help="only the multi-scale SSIM legs")
     ap.add_argument("--yuv", action="store_true", help="only the colour-conversion legs")
     ap.add_argument("--scene", action="store_true", help="only the scene-cut legs")
+    ap.add_argument("--tile", action="store_true", help="only the tiled-synthesis legs")
     a = ap.parse_args()
+    if a.tile:
+        dev = torch.device("cuda:0")
+        res = dict(tile_blend_2160x3840=tile_blend_numbers(dev, a.seconds))
+        torch.cuda.empty_cache()
+        res["tile_forward"] = tile_forward_numbers(dev, a.seconds)
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.scene:
         res = dict(scene=scene_numbers(torch.device("cuda:0"), a.seconds))
         print(json.dumps(res, indent=1))
