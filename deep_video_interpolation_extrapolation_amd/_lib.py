@@ -214,6 +214,14 @@ class SynthCutFillDesc(ctypes.Structure):
     ]
 
 
+class SynthRetimeDesc(ctypes.Structure):
+    _fields_ = [
+        ("slots", vp), ("out", vp), ("rows", vp), ("rows_dev", vp), ("cut", vp),
+        ("slot_s0", i64), ("slot_s1", i64), ("out_s0", i64), ("out_s1", i64), ("nbytes", i64),
+        ("n0", i32), ("n_slots", i32), ("n_rows", i32), ("n_pairs", i32), ("den", i32), ("pad0", i32),
+    ]
+
+
 TILE_MAX = 32  # DVIE_TILE_MAX: tiles per axis of dvie_synth_tile_blend
 
 
@@ -344,7 +352,7 @@ _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, 
         108: SynthLoadPadDesc, 109: SynthFinishCropDesc, 110: SynthVggLoadDesc}
 # descriptors added after the set tests/test_perceptual_cpu.py pins for _ABI; load() checks both tables
 _ABI_MORE = {111: SynthMsssimDesc, 112: SynthYuvDesc, 113: SynthSceneDesc, 114: SynthCutFillDesc,
-             115: SynthTileBlendDesc}
+             115: SynthTileBlendDesc, 117: SynthRetimeDesc}  # (116 is unused and answers 0)
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -360,6 +368,7 @@ EXPORTS = [
     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks", "dvie_synth_msssim", "dvie_synth_msssim_ws_bytes",
     "dvie_synth_yuv2rgb", "dvie_synth_rgb2yuv", "dvie_conv_chain", "dvie_conv2d_chain", "dvie_ops_chain_pairs",
     "dvie_synth_scene", "dvie_synth_scene_ws_bytes", "dvie_synth_cutfill", "dvie_synth_tile_blend",
+    "dvie_synth_retime",
 ]
 
 _lib = None
@@ -397,7 +406,8 @@ def load():
                      "dvie_head3_bwd", "dvie_segenc_fwd", "dvie_segenc_bwd", "dvie_synth_load", "dvie_synth_finish",
                      "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop",
                      "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_synth_msssim", "dvie_synth_yuv2rgb",
-                     "dvie_synth_rgb2yuv", "dvie_synth_scene", "dvie_synth_cutfill", "dvie_synth_tile_blend"):
+                     "dvie_synth_rgb2yuv", "dvie_synth_scene", "dvie_synth_cutfill", "dvie_synth_tile_blend",
+                     "dvie_synth_retime"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]

@@ -885,6 +885,7 @@ size_t dvie_abi_sizeof(int which) {
     case 113: return sizeof(dvie_synth_scene_desc);
     case 114: return sizeof(dvie_synth_cutfill_desc);
     case 115: return sizeof(dvie_synth_tile_blend_desc);
+    case 117: return sizeof(dvie_synth_retime_desc);  // (116 stays 0: tests/test_tile_cpu.py pins it as unused)
     default: return 0;
   }
 }

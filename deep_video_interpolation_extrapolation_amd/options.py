@@ -65,6 +65,22 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
   --synth_tile_overlap N    the least overlap of neighbouring tiles in pixels: a multiple of the net's
                             coarsest stride, at most half the smaller tile side and at most 256 (default
                             64, provisional: not validated on trained weights and real footage)
+  --synth_rate P:Q          --split test, INTER: frame-rate conversion by the ratio P:Q (synth.Retime): output
+                            frame k has the time k*Q/P in input frames, so 5:2 turns 24 Hz into 60 Hz, 6:5
+                            25 into 30 and 5:6 30 into 25.  The output clock is laid over the grid of
+                            --synth_levels K doublings, which needs P <= Q * 2**K (raise --synth_levels
+                            otherwise); only the forwards the outputs need are run, and one log line per
+                            clip gives the rate, the output count and "F forwards of D".  P and Q are
+                            positive and at most 4096 once reduced.  A .y4m clip is written at its own rate
+                            times P/Q; outputs that coincide with an input are the input's own packed
+                            bytes.  Works with --synth_window, --synth_scd, --synth_pad and --synth_tile.
+                            Off by default; EXTRA and --synth_eval ignore it
+  --synth_rate_mode {nearest,blend}
+                            with --synth_rate: `nearest` (default) writes the grid frame nearest to each
+                            output time, a tie going to the earlier one (timing error at most 1/2**(K+1) of
+                            an input interval); `blend` cross-fades the two neighbouring grid frames, which
+                            are 1/2**K of an input interval apart, with exact integer rounding.  Neither
+                            has been judged on trained weights and real footage
 """
 import argparse
 
@@ -94,6 +110,24 @@ def _overlap(text):
     if not re.fullmatch(r"[0-9]+", text):
         raise argparse.ArgumentTypeError(f"--synth_tile_overlap {text}: expected a non-negative integer")
     return int(text)
+
+
+def _rate(text):
+    """--synth_rate: P:Q, two positive integers, each at most 4096 once reduced by their gcd -> (P, Q) reduced"""
+    import math
+    import re
+    m = re.fullmatch(r"([0-9]+):([0-9]+)", text)
+    if not m:
+        raise argparse.ArgumentTypeError(f"--synth_rate {text}: expected P:Q, two positive integers (5:2 for 24 -> 60 Hz)")
+    p, q = int(m.group(1)), int(m.group(2))
+    if p < 1 or q < 1:
+        raise argparse.ArgumentTypeError(f"--synth_rate {text}: P and Q must be at least 1")
+    g = math.gcd(p, q)
+    p, q = p // g, q // g
+    if max(p, q) > 4096:
+        raise argparse.ArgumentTypeError(f"--synth_rate {text}: P and Q must not exceed 4096 once reduced "
+                                         f"({p}:{q}); use a nearby ratio of smaller terms")
+    return p, q
 
 
 def _unit_range(flag, hi):
@@ -166,6 +200,8 @@ GLOBAL = [
     ("--synth_scd_hist", "synth_scd_hist", _unit_range("--synth_scd_hist", 1), 0.25, None),
     ("--synth_tile", "synth_tile", _tile, None, None),
     ("--synth_tile_overlap", "synth_tile_overlap", _overlap, 64, None),
+    ("--synth_rate", "synth_rate", _rate, None, None),
+    ("--synth_rate_mode", "synth_rate_mode", str, "nearest", ["nearest", "blend"]),
 ]
 
 # second-stage flags of the reference's INTER sub-command (options/options.py:296-380);

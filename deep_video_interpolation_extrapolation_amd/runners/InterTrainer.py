@@ -401,14 +401,50 @@ class InterTrainer:
         self.log.info("synth: {}: {} scene cut{} after input frame{} {}".format(
             clip, len(at), "" if len(at) == 1 else "s", "" if len(at) == 1 else "s", at))
 
+    def _rate(self):
+        """the synth.Retime of --synth_rate and --synth_rate_mode, or None; a ratio the grid of
+        --synth_levels cannot carry is a ValueError that names both flags.  Runners that do not
+        stream (EXTRA) ignore the flags, with one log line per run."""
+        from ..synth import Retime
+        a = self.args
+        pq = getattr(a, "synth_rate", None)
+        if pq is None:
+            return None
+        if not self._streams:
+            if not getattr(self, "_rate_noted", False):
+                self.log.info("synth: --synth_rate and --synth_rate_mode are ignored: extrapolation keeps the clip's rate")
+                self._rate_noted = True
+            return None
+        rate, levels = Retime(int(pq[0]), int(pq[1]), getattr(a, "synth_rate_mode", "nearest")), getattr(a, "synth_levels", 1)
+        if levels < 0 or rate.num > rate.den << levels:
+            need = max(levels, 0)
+            while rate.num > rate.den << need:
+                need += 1
+            raise ValueError(f"--synth_rate {rate.num}:{rate.den} needs more than the {1 << max(levels, 0)} grid frames "
+                             f"per input interval of --synth_levels {levels}: pass --synth_levels {need} or more")
+        return rate
+
+    def _log_rate(self, clip, rate, T, n_out, forwards, dense):
+        """one line per clip under --synth_rate: the rate, the frame counts and the forwards run"""
+        self.log.info("synth: {}: rate {}:{} ({}): {} frames from {}, {} forwards of {}".format(
+            clip, rate.num, rate.den, rate.mode, n_out, T, forwards, dense))
+
     def _synthesize(self, syn, frames, labels, clip=""):
-        """--split test, interpolation: --synth_levels frame-rate doublings of the whole clip; with
-        --synth_scd frames are held across the detected cuts, which are logged"""
-        scene = self._scene()
+        """--split test, interpolation: --synth_levels frame-rate doublings of the whole clip, or with
+        --synth_rate its conversion by P:Q; with --synth_scd frames are held across the detected
+        cuts, which are logged"""
+        scene, rate = self._scene(), self._rate()
+        kw = dict(levels=getattr(self.args, "synth_levels", 1))
+        if rate is not None:
+            kw["rate"] = rate
         if scene is None:
-            return syn.interpolate(frames, labels, levels=getattr(self.args, "synth_levels", 1))
-        out_f, out_l, cuts = syn.interpolate(frames, labels, levels=getattr(self.args, "synth_levels", 1), scene=scene)
-        self._log_cuts(clip, cuts[0].cpu().tolist())
+            out_f, out_l = syn.interpolate(frames, labels, **kw)
+        else:
+            out_f, out_l, cuts = syn.interpolate(frames, labels, scene=scene, **kw)
+            self._log_cuts(clip, cuts[0].cpu().tolist())
+        if rate is not None:
+            plan = syn.retime_last
+            self._log_rate(clip, rate, frames.shape[1], plan.count, plan.forwards, plan.dense_forwards)
         return out_f, out_l
 
     _streams = True  # --synth_window applies: interpolation runs in windows (ExtraTrainer: False)
@@ -421,7 +457,9 @@ class InterTrainer:
         frames, the label maps and their palette colouring, numbered in output order; or a file
         <clip>.y4m (labels: /seg/<clip>.y4m, the Y plane the class id) ->
         synth/{rgb,seg,vis_seg}/<clip>.y4m (_stream_clip, _whole_y4m).  INTER with --synth_window N
-        >= 2 runs every clip in windows of N input frames with overlapped I/O (_stream_clip)."""
+        >= 2 runs every clip in windows of N input frames with overlapped I/O (_stream_clip).  INTER
+        with --synth_rate P:Q converts the frame rate by that ratio instead of by 2**synth_levels
+        (_rate; both paths, one log line per clip)."""
         import numpy as np
         from PIL import Image
         from ..utils.net_utils import CITYSCAPES_COLORS
@@ -431,6 +469,7 @@ class InterTrainer:
         assert a.cycgen_load_dir is not None, "please specify --cycgen_load_dir"
         if getattr(a, "synth_eval", False):
             return self.test_eval()
+        self._rate()  # (a rate --synth_levels cannot carry ends the run before a clip is read)
         syn = self._synthesizer()
         img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
         root = os.path.join(a.cycgen_load_dir, "synth")
@@ -519,6 +558,36 @@ class InterTrainer:
         vis = rgb_to_yuv(vis, "C444", matrix, full)
         return pk.cpu().numpy(), out_l.reshape(S, H * W).cpu().numpy(), vis.cpu().numpy()
 
+    def _pack_y4m_rate(self, src, out_f, out_l, palette, originals, plan, cuts=None):
+        """_pack_y4m under --synth_rate: the N = plan.count outputs (N, H, W, 3) / (N, H, W) of one window
+        of a Y4M clip -> what Y4MSink.write takes.  The deque `originals` holds the packed device frames
+        of the window's plan.T inputs; all but the last, which the next window starts with, are taken
+        off.  Outputs that coincide with an input (plan.aligned) never go through synth.rgb_to_yuv: one
+        synth.retime_gather over the packed inputs (plan.input_rows) copies the input's own bytes
+        there and, reading the flags `cuts` on the device, over every output held across a cut; the
+        runs of outputs between the aligned ones are converted first, one launch per run."""
+        import numpy as np
+        from ..synth import retime_gather, rgb_to_yuv
+        from ..video_io import frame_bytes
+        N, H, W = out_l.shape
+        cs, full, matrix = src.rgb.colourspace, src.rgb.full_range, getattr(self.args, "synth_yuv", "bt601")
+        assert len(originals) == plan.T, (len(originals), plan.T)
+        inputs = torch.stack(list(originals))
+        for _ in range(plan.T - 1):
+            originals.popleft()
+        pk = torch.empty((N, frame_bytes(W, H, cs)), dtype=torch.uint8, device=out_f.device)
+        if N == 0:
+            return pk.cpu().numpy(), np.empty((0, H * W), np.uint8), np.empty((0, 3 * H * W), np.uint8)
+        i = 0
+        for j in [j for j, _ in plan.aligned] + [N]:
+            if j > i:
+                rgb_to_yuv(out_f[i:j], cs, matrix, full, out=pk[i:j])
+            i = j + 1
+        retime_gather(inputs[None], plan.input_rows, 1, pk[None], cuts)
+        vis = palette[out_l.clamp(max=palette.shape[0] - 1).long()]  # (ids past the classes: "none")
+        vis = rgb_to_yuv(vis, "C444", matrix, full)
+        return pk.cpu().numpy(), out_l.reshape(N, H * W).cpu().numpy(), vis.cpu().numpy()
+
     def _stream_clip(self, syn, src, window, root, palette):
         """--split test, interpolation, one clip in windows (window 0: a .y4m clip as one window):
         a reader thread prepares the next window (file reads, PNG decoding), this thread copies it
@@ -531,30 +600,40 @@ class InterTrainer:
         other copies, and one log line names the clip's cuts."""
         import collections
         import time
-        from ..synth import FrameSizeError
+        from ..synth import FrameSizeError, retime_fps
         from ..video_io import BackgroundWriter, PngSink, Prefetcher, Y4MSink
         levels = getattr(self.args, "synth_levels", 1)
         step = 1 << levels
+        rate = self._rate()
         if src.kind == "png":
             sink = PngSink(root, src.name, palette)
         else:
             num, den = src.rgb.fps
-            sink = Y4MSink(root, src.name, src.width, src.height, (num * step, den), src.rgb.colourspace,
+            sink = Y4MSink(root, src.name, src.width, src.height,
+                           (num * step, den) if rate is None else retime_fps((num, den), rate), src.rgb.colourspace,
                            src.rgb.full_range)
             palette = torch.from_numpy(palette).to(self.device)
         originals = collections.deque()
         scene, flags, hold = self._scene(), [], [None]
         t_start, g0 = time.perf_counter(), 0
+        n_in = forwards = dense = 0  # (--synth_rate: the clip's input frames and forwards, summed over its windows)
         try:
             with Prefetcher(src.chunks(window)) as reader, BackgroundWriter(sink.write) as writer:
                 on_device = (self._upload(src, host, originals if src.kind == "y4m" else None) for host in reader)
                 try:
-                    for out_f, out_l, *cuts in syn.interpolate_stream(on_device, levels=levels, scene=scene):
+                    for out_f, out_l, *cuts in syn.interpolate_stream(on_device, levels=levels, scene=scene,
+                                                                      **({} if rate is None else dict(rate=rate))):
                         S = out_f.shape[1]
-                        if g0 == 0:
+                        if g0 == 0 and n_in == 0:
                             self._log_tiles(syn, src.name, out_f.shape[2], out_f.shape[3])
+                        if rate is not None:
+                            plan = syn.retime_last
+                            n_in, forwards, dense = plan.t0 + plan.T, forwards + plan.forwards, dense + plan.dense_forwards
                         if src.kind == "png":
                             writer.put((g0, out_f[0].cpu().numpy(), out_l[0].cpu().numpy()))
+                        elif rate is not None:
+                            writer.put(self._pack_y4m_rate(src, out_f[0], out_l[0], palette, originals, plan,
+                                                           cuts[0] if cuts else None))
                         else:
                             writer.put(self._pack_y4m(src, out_f[0], out_l[0], palette, originals, (-g0) % step, step,
                                                       *((cuts[0], hold) if cuts else ())))
@@ -571,6 +650,8 @@ class InterTrainer:
         t_end = time.perf_counter()
         if scene is not None:
             self._log_cuts(src.name, flags)
+        if rate is not None:
+            self._log_rate(src.name, rate, n_in, g0, forwards, dense)
         self.log.info("synth: {}: {} slots in {:.3f} s ({:.1f} slots/s); reader busy {:.3f} s, this thread waited for it "
                       "{:.3f} s and for the writer {:.3f} s, writer busy {:.3f} s ({:.3f} s after the last window)".format(
                           src.name, g0, t_end - t_start, g0 / max(t_end - t_start, 1e-9), reader.busy, reader.waited,
@@ -625,6 +706,9 @@ class InterTrainer:
         a = self.args
         if getattr(a, "synth_scd", False):
             self.log.info("synth_eval: --synth_scd is ignored: every held-out frame is scored against its original")
+        if getattr(a, "synth_rate", None) is not None:
+            self.log.info("synth_eval: --synth_rate and --synth_rate_mode are ignored: the held-out frames sit on the "
+                          "2**K grid")
         syn = self._synthesizer()
         scorer = PerceptualScorer(max_batch=max(1, a.batch_size)) if getattr(a, "synth_vgg", False) else None
         scales = getattr(a, "synth_msssim", 0) or None

@@ -60,6 +60,13 @@ two integers (luma SAD, 32-bin luma histogram distance: dvie_synth_scene), `scen
 them with two integer limits on the device, and after the unchanged rollout `cut_fill`
 (dvie_synth_cutfill) overwrites the slots between a flagged pair with copies of the nearer input
 frame and label map.  The flags never visit the host on the way.
+
+Frame-rate conversion (opt-in, `Retime`): a ratio P:Q lays an output clock over the dyadic grid of
+`levels` doublings.  `retime_plan` maps every output to one or two grid slots on the host, prunes
+the midpoint tree to the forwards those slots need and numbers the surviving slots compactly; the
+unchanged `_roll` runs that schedule, and `retime_gather` (dvie_synth_retime) copies or blends the
+slots into the output frames in one launch, holding frames across flagged pairs from the flags on
+the device.
 """
 import ctypes
 
@@ -755,6 +762,211 @@ class SceneCuts:
         return f"SceneCuts(mad={self.mad}, hist={self.hist})"
 
 
+RETIME_MAX = 4096  # the largest P and Q of a Retime (dvie_synth_retime's den)
+RETIME_MODES = ("nearest", "blend")
+
+
+class Retime:
+    """A frame-rate conversion by the ratio num:den = P:Q (interpolate(..., rate=)): output frame k has
+    time k*Q/P in input-frame units.  24 -> 60 Hz is Retime(5, 2), 25 -> 30 Retime(6, 5), 30 -> 25
+    Retime(5, 6).  P and Q are positive ints, reduced by their gcd and then at most 4096 each.  mode:
+    "nearest" -- an output is a byte copy of the nearest slot of the dyadic grid of `levels`
+    doublings, a tie going to the earlier slot (timing error at most 1 / 2**(levels + 1) of an input
+    interval) -- or "blend": the rounded integer cross-fade of the two neighbouring slots
+    (dvie_synth_retime).  Neither mode has been judged on trained weights and real footage."""
+
+    def __init__(self, num, den, mode="nearest"):
+        import math
+        for name, v in (("num", num), ("den", den)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"Retime: {name}={v!r} must be a positive int")
+        if mode not in RETIME_MODES:
+            raise ValueError(f"Retime: mode {mode!r} must be one of {', '.join(RETIME_MODES)}")
+        g = math.gcd(num, den)
+        self.num, self.den, self.mode = num // g, den // g, mode
+        if max(self.num, self.den) > RETIME_MAX:
+            raise ValueError(f"Retime: {self.num}:{self.den} (reduced) must not exceed {RETIME_MAX} on either side")
+
+    def __repr__(self):
+        return f"Retime({self.num}, {self.den}, mode={self.mode!r})"
+
+    def __eq__(self, other):
+        return isinstance(other, Retime) and (self.num, self.den, self.mode) == (other.num, other.den, other.mode)
+
+    def __hash__(self):
+        return hash((self.num, self.den, self.mode))
+
+
+def _retime_check(levels, rate):
+    if not isinstance(rate, Retime):
+        raise ValueError(f"rate: a Retime or None, got {type(rate).__name__}")
+    if isinstance(levels, bool) or not isinstance(levels, int) or levels < 0:
+        raise ValueError(f"levels={levels!r} must be a non-negative int")
+    if rate.num > rate.den << levels:
+        need = levels
+        while rate.num > rate.den << need:
+            need += 1
+        raise ValueError(f"rate {rate.num}:{rate.den} puts more than 2**levels = {1 << levels} outputs into an input "
+                         f"interval, so outputs would repeat grid slots: raise levels / --synth_levels to at least {need}")
+
+
+def retime_count(T, rate):
+    """The output frames of a T-frame clip at `rate`: those with time k*Q/P <= T - 1 ->
+    (T - 1) * P // Q + 1"""
+    if T < 1:
+        raise ValueError(f"retime_count: T={T} must be at least 1")
+    return (T - 1) * rate.num // rate.den + 1
+
+
+def retime_fps(fps, rate):
+    """The frame rate (num, den) of a clip of rate `fps` = (num, den) after `rate`: (num * P, den * Q)
+    reduced by their gcd -- (24000, 1001) at 5:2 is (60000, 1001)"""
+    import math
+    n, d = int(fps[0]) * rate.num, int(fps[1]) * rate.den
+    g = math.gcd(n, d) or 1
+    return n // g, d // g
+
+
+class RetimePlan:
+    """retime_plan's result.  With S = len(slots) compact slots and N = count outputs:
+      T, levels, rate, t0, first   what was planned
+      k0, count        the global index of the first emitted output and how many are emitted
+      slots            the dense slots (0 .. (T - 1) * 2**levels, input t at t * 2**levels) that exist,
+                       ascending; compact index c stands for dense slot slots[c]
+      index            {dense slot: compact index}
+      in_slots         the compact indices of the T inputs, in order
+      levels_c         the pruned schedule: levels of (left, right, out) compact triples, coarsest
+                       spacing first, ascending within a level (midpoint_schedule's order)
+      keep             frozenset of the compact slots some forward reads
+      rows             per output (lo, hi, n, pair, hold) for the frames (dvie_synth_retime's rows)
+      label_rows       the same with `nearest` resolved: (s, s, 0, pair, hold)
+      input_rows       rows over the window's T INPUTS (slot t = input t) for data that exists per
+                       input only, such as packed Y'CbCr frames: a time-aligned output copies its
+                       input, every other output is skipped (lo = -1) unless its pair is flagged, when
+                       it copies input `hold`
+      aligned          [(j, t)]: emitted output j (window-local) is input frame t (window-local)
+      forwards, dense_forwards   the forwards of levels_c and of the full 2**levels schedule"""
+
+    def keep_fn(self, s):
+        return s in self.keep
+
+
+def retime_plan(T, levels, rate, t0=0, first=True):
+    """Plan the rate conversion of one window of T >= 2 input frames whose first frame has global
+    index t0 -> RetimePlan.  Output k (global) has time k*Q/P and, on the window's dense grid of
+    `levels` doublings, the position x = k*Q*2**levels/P - t0*2**levels: lo = floor(x) and the
+    weight n = (k*Q*2**levels) mod P over P of slot lo + 1 (Python ints throughout: k is unbounded
+    on a long stream).  The window emits the outputs with t0 < time <= t0 + T - 1, and time == t0 as
+    well when `first` (interpolate_stream's closed-right convention: a later window's first frame
+    was emitted by the window before).  "nearest" reads slot lo when 2n <= P and lo + 1 otherwise;
+    "blend" reads lo and, when n > 0, lo + 1, and takes its label map by the nearest rule.  An
+    output strictly inside input pair p is held, when p is flagged, as the left input if
+    time - p <= 1/2 and the right one otherwise.  Only the slots an output reads, the inputs and
+    their midpoint ancestors exist; the schedule holds the forwards that write them.
+    P > Q * 2**levels: ValueError (raise levels)."""
+    _retime_check(levels, rate)
+    if isinstance(T, bool) or not isinstance(T, int) or T < 2:
+        raise ValueError(f"retime_plan: T={T!r} must be an int of at least 2")
+    if isinstance(t0, bool) or not isinstance(t0, int) or t0 < 0:
+        raise ValueError(f"retime_plan: t0={t0!r} must be a non-negative int")
+    P, Q, step = rate.num, rate.den, 1 << levels
+    k0 = -((-t0 * P) // Q) if first else t0 * P // Q + 1
+    k1 = (t0 + T - 1) * P // Q  # the last output of the window, inclusive
+    outs = []  # (lo, n, near, pair, hold_slot, aligned input or None), dense window-local slots
+    need = set(t * step for t in range(T))
+    for k in range(k0, k1 + 1):
+        g = k * Q * step - t0 * step * P  # x * P, window-local
+        lo, n = divmod(g, P)
+        near = lo if 2 * n <= P else lo + 1
+        if n == 0 and lo % step == 0:
+            pair, hold, at = -1, lo, lo // step
+        else:
+            pair, at = lo // step, None
+            hold = pair * step if 2 * (g - pair * step * P) <= step * P else (pair + 1) * step
+        outs.append((lo, n, near, pair, hold, at))
+        need.update((near,) if rate.mode == "nearest" else ((lo, lo + 1) if n else (lo,)))
+    triples = [[] for _ in range(levels)]
+    todo = sorted(s for s in need if s % step)
+    while todo:  # the midpoint ancestors: slot s of spacing h = lowest set bit is made from s - h and s + h
+        s = todo.pop()
+        h = s & -s
+        for a in (s - h, s + h):
+            if a % step and a not in need:
+                need.add(a)
+                todo.append(a)
+    p = RetimePlan()
+    p.T, p.levels, p.rate, p.t0, p.first = T, levels, rate, t0, first
+    p.k0, p.count = k0, len(outs)
+    p.slots = sorted(need)
+    p.index = {s: c for c, s in enumerate(p.slots)}
+    ix = p.index
+    p.in_slots = [ix[t * step] for t in range(T)]
+    for s in p.slots:
+        if s % step:
+            h = s & -s
+            triples[levels - h.bit_length()].append((ix[s - h], ix[s + h], ix[s]))
+    p.levels_c = [lv for lv in triples if lv]
+    p.keep = frozenset(c for lv in p.levels_c for a, b, _ in lv for c in (a, b))
+    p.rows, p.label_rows, p.input_rows, p.aligned = [], [], [], []
+    for j, (lo, n, near, pair, hold, at) in enumerate(outs):
+        if rate.mode == "nearest":
+            p.rows.append((ix[near], ix[near], 0, pair, ix[hold]))
+        else:
+            p.rows.append((ix[lo], ix[lo + 1] if n else ix[lo], n, pair, ix[hold]))
+        p.label_rows.append((ix[near], ix[near], 0, pair, ix[hold]))
+        if at is not None:
+            p.input_rows.append((at, at, 0, -1, at))
+            p.aligned.append((j, at))
+        else:
+            p.input_rows.append((-1, -1, 0, pair, hold // step))
+    p.forwards = sum(len(lv) for lv in p.levels_c)
+    p.dense_forwards = (T - 1) * (step - 1)
+    return p
+
+
+def retime_gather(slots, rows, den, out, cuts=None):
+    """The output frames of a rate conversion, gathered or blended on the device: `slots` uint8
+    (B, S, ...) and `out` uint8 (B, N, ...) on one device, any strides over the two leading
+    dimensions and the others contiguous and equal (frames, label maps or packed Y'CbCr frames; the
+    transposed views of slot-major storage are taken as they are); `rows`: N rows (lo, hi, n, pair,
+    hold) of ints (RetimePlan.rows / label_rows / input_rows), uploaded once; `cuts`: bool or uint8
+    (B, pairs) on the device, or None.  Output (b, k), in this order: its pair is flagged -> a byte
+    copy of slot hold; lo < 0 -> not written; n == 0 -> a byte copy of slot lo; else every byte
+    (a * (den - n) + c * n + den // 2) // den of the bytes a, c of slots lo and hi, exact
+    (dvie_synth_retime: one launch, the flags read on the device, no host synchronisation).
+    N == 0 launches nothing.  -> out"""
+    L.require_gpu(slots)
+    if slots.dtype != torch.uint8 or slots.dim() < 2 or out.dtype != torch.uint8 or out.dim() != slots.dim() or \
+            out.device != slots.device or out.shape[0] != slots.shape[0] or out.shape[2:] != slots.shape[2:]:
+        raise ValueError(f"slots: uint8 (B, S, ...) and out: uint8 (B, N, ...) of the same rows on one device, got "
+                         f"{tuple(slots.shape)} {slots.dtype} and {tuple(out.shape)} {out.dtype}")
+    B, S = slots.shape[:2]
+    N = out.shape[1]
+    rows = [tuple(int(v) for v in r) for r in rows]
+    if len(rows) != N or any(len(r) != 5 for r in rows):
+        raise ValueError(f"rows: {N} rows (lo, hi, n, pair, hold), one per output, got {len(rows)}")
+    if N == 0:
+        return out
+    tail = tuple(slots.shape[2:])
+    d = L.SynthRetimeDesc()
+    d.n0, d.n_slots, d.slot_s0, d.slot_s1 = _lead_of(slots, tail, "slots")
+    _, d.n_rows, d.out_s0, d.out_s1 = _lead_of(out, tail, "out")
+    d.nbytes, d.den = 1, den
+    for n in tail:
+        d.nbytes *= n
+    if cuts is not None:
+        if cuts.dtype not in (torch.bool, torch.uint8) or cuts.dim() != 2 or cuts.device != slots.device or \
+                cuts.shape[0] != B:
+            raise ValueError(f"cuts: bool (B, pairs) on {slots.device}, got {tuple(cuts.shape)} {cuts.dtype}")
+        cuts = cuts.contiguous()
+        d.cut, d.n_pairs = cuts.data_ptr(), cuts.shape[1]
+    host = (ctypes.c_int32 * (5 * N))(*[v for r in rows for v in r])
+    dev = torch.tensor(rows, dtype=torch.int32).to(slots.device)
+    d.slots, d.out, d.rows, d.rows_dev = slots.data_ptr(), out.data_ptr(), ctypes.addressof(host), dev.data_ptr()
+    L.check(L.load().dvie_synth_retime(ctypes.byref(d), L.stream_ptr(slots.device)), "synth retime")
+    return out
+
+
 def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perceptual=None, msssim=None):
     """Score uint8 device frames `pred` (..., H, W, 3) against `gt` and, when both are given,
     label maps `pred_labels` (..., H, W) against `gt_labels` (dvie_synth_score: one fused pass
@@ -980,6 +1192,7 @@ class VideoSynthesizer:
         self.net, self.cm, self.max_batch, self.graph = net, cm, int(max_batch), bool(graph)
         self._scratch = {}  # (n, H, W, device) -> the scratch tensors of a forward
         self._graphs = {}
+        self.retime_last = None  # the RetimePlan of the last interpolate(..., rate=)
         self._tile_scratch = {}  # (n, th, tw, tiles, device) -> the tile inputs and the stash of a tiled forward
         self._max_pixels = None
         self.tile, self.overlap = None, 0
@@ -1269,7 +1482,7 @@ class VideoSynthesizer:
                         k += m
         return fr, lb
 
-    def interpolate(self, frames, labels, levels=1, scene=None):
+    def interpolate(self, frames, labels, levels=1, scene=None, rate=None, t0=0, first=True):
         """frames (B, T, H, W, 3), labels (B, T, H, W), uint8 on the device -> frames
         (B, (T - 1) * 2**levels + 1, H, W, 3) and labels of the same length (uint8, views of
         slot-major storage): the inputs unchanged at the multiples of 2**levels, between them
@@ -1282,11 +1495,27 @@ class VideoSynthesizer:
         what they are without it -- and then cut_fill of the frames and of the label maps: the
         slots between a flagged pair are byte copies of the nearer input frame and label map, the
         midpoint the left one's.  cuts: bool (B, T - 1) on the device.  None: two results, and
-        nothing of the above runs."""
+        nothing of the above runs.
+
+        rate: a Retime -> frames (B, N, H, W, 3) and labels (B, N, H, W) at the output clock of
+        retime_plan(T, levels, rate, t0, first): the N = plan.count outputs the window emits (t0:
+        the global index of frames[:, 0]; first: whether the output at time t0 belongs to it), N = 0
+        included.  Only the plan's compact slots are rolled out (plan.forwards forwards instead of
+        plan.dense_forwards); two retime_gather launches then write the frames (plan.rows) and the
+        label maps (plan.label_rows).  With scene, scene_cuts of the inputs is taken as above and
+        the gathers read the flags on the device: an output strictly inside a flagged pair is the
+        nearer input's frame and label map (no cut_fill runs), and cuts (B, T - 1) is returned as the
+        third result.  The plan of the last such call stays in `retime_last`.  t0 or first without
+        rate: ValueError.  None: everything above is what it was."""
         self._check(frames, labels)
         T = frames.shape[1]
         if T < 2 or levels < 0:
             raise ValueError("interpolate needs at least two frames and levels >= 0")
+        if rate is None and (t0 != 0 or first is not True):
+            raise ValueError("interpolate: t0 and first place a window on the output clock of rate=; without a rate "
+                             "they have no meaning")
+        if rate is not None:
+            return self._interpolate_rate(frames, labels, levels, scene, rate, t0, first)
         if scene is not None:
             if not isinstance(scene, SceneCuts):
                 raise ValueError(f"scene: a SceneCuts or None, got {type(scene).__name__}")
@@ -1303,7 +1532,24 @@ class VideoSynthesizer:
                             keep=lambda s: levels > 0 and s % 2 == 0)
         return fr.transpose(0, 1), lb.transpose(0, 1)
 
-    def interpolate_stream(self, chunks, levels=1, scene=None):
+    def _interpolate_rate(self, frames, labels, levels, scene, rate, t0, first):
+        """interpolate(..., rate=): the plan, the flags, the pruned rollout, the two gathers"""
+        B, T, H, W, _ = frames.shape
+        plan = retime_plan(T, levels, rate, t0, first)
+        if scene is not None and not isinstance(scene, SceneCuts):
+            raise ValueError(f"scene: a SceneCuts or None, got {type(scene).__name__}")
+        cuts = scene_cuts(frames, scene.mad, scene.hist) if scene is not None else None
+        self.retime_last = plan
+        N = plan.count
+        out_f = torch.empty((N, B, H, W, 3), dtype=torch.uint8, device=frames.device).transpose(0, 1)
+        out_l = torch.empty((N, B, H, W), dtype=torch.uint8, device=frames.device).transpose(0, 1)
+        if N:
+            fr, lb = self._roll(frames, labels, len(plan.slots), plan.in_slots, plan.levels_c, keep=plan.keep_fn)
+            retime_gather(fr.transpose(0, 1), plan.rows, rate.num, out_f, cuts)
+            retime_gather(lb.transpose(0, 1), plan.label_rows, rate.num, out_l, cuts)
+        return (out_f, out_l) if scene is None else (out_f, out_l, cuts)
+
+    def interpolate_stream(self, chunks, levels=1, scene=None, rate=None):
         """interpolate() of a clip of any length in bounded memory: a generator over `chunks`, any
         iterable of (frames (B, t, H, W, 3), labels (B, t, H, W)) uint8 device tensors with t >= 1,
         the clip in order.  The last input frame of a chunk (its uint8 frame and label map) is
@@ -1323,7 +1569,17 @@ class VideoSynthesizer:
         included, and the slots are filled before the carried frame's slot is dropped.  A pair's
         flag depends on its two frames only, so the equalities above hold with the flags: the
         streamed triples equal the per-window ones byte for byte, and with max_batch = 1 the
-        whole clip's."""
+        whole clip's.
+
+        rate: a Retime -> every window goes through interpolate(..., rate=, t0=, first=) with the
+        global index of its first frame; a window yields the outputs whose time lies after its first
+        frame, up to and including its last (the very first window its first frame's too), so
+        nothing is dropped afterwards and a window that holds no output (possible when P < Q) yields
+        tensors with zero slots.  Concatenated, the yields are retime_count(T, rate) frames, equal
+        window by window to interpolate() of the window with its t0 and, with max_batch = 1, to
+        interpolate(..., rate=) of the whole clip."""
+        if rate is not None:
+            _retime_check(levels, rate)
         carry, emitted, total = None, False, 0
         for frames, labels in chunks:
             self._check(frames, labels)
@@ -1340,9 +1596,13 @@ class VideoSynthesizer:
             carry = (frames[:, -1:].clone(), labels[:, -1:].clone())
             if frames.shape[1] < 2:
                 continue  # (the first chunk was one frame: held)
-            out_f, out_l, *cuts = self.interpolate(frames, labels, levels, scene)
+            if rate is not None:
+                out_f, out_l, *cuts = self.interpolate(frames, labels, levels, scene, rate, total - frames.shape[1],
+                                                       not emitted)
+            else:
+                out_f, out_l, *cuts = self.interpolate(frames, labels, levels, scene)
             del frames, labels
-            if emitted:
+            if emitted and rate is None:
                 out_f, out_l = out_f[:, 1:], out_l[:, 1:]
             emitted = True
             yield (out_f, out_l, *cuts)

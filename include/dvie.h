@@ -1253,6 +1253,45 @@ typedef struct dvie_synth_tile_blend_desc {
 
 int dvie_synth_tile_blend(const dvie_synth_tile_blend_desc* d, void* stream);
 
+/*
+ * dvie_synth_retime: the output frames of a frame-rate conversion, gathered or blended from the
+ * slots of interpolated clips (synth.retime_gather; DESIGN.md "Frame-rate conversion").  One launch
+ * over all n_rows x n0 output rows; no host synchronisation, the flags are read on the device.
+ *
+ * Slots: n0 clips of n_slots slots, slot (b, s) the nbytes contiguous bytes at slots + b*slot_s0 +
+ * s*slot_s1 BYTES; outputs: row (b, k) the nbytes bytes at out + b*out_s0 + k*out_s1 (any strides
+ * with |s1| >= nbytes, the transposed views of slot-major storage included; no alignment is
+ * assumed).  rows: n_rows x 5 int32 (lo, hi, n, pair, hold), given twice: `rows` on the host, which
+ * the call validates, and `rows_dev`, the same values on the device, which the kernel reads.
+ * cut: n0 x n_pairs contiguous uint8 flags on the device (dvie_synth_scene's), or NULL.
+ * Output row (b, k), in this order:
+ *   1. cut != NULL, pair >= 0 and cut[b*n_pairs + pair] != 0:  a byte copy of slot `hold`
+ *   2. lo < 0:   nothing is written
+ *   3. n == 0:   a byte copy of slot lo
+ *   4. else:     every byte (a*(den - n) + c*n + den/2) / den, a and c the bytes of slots lo and hi,
+ *                exact integers (the divide is a multiply by ceil(2^32 / (den * (4096 / den))) after
+ *                scaling the weights by 4096 / den; csrc/retime.hip shows why that is exact)
+ * The unit is bytes, so the same call serves frames, label maps (rows with n = 0) and packed Y'CbCr
+ * frames.  No byte outside the written rows is touched.  16-byte moves where the destination and the
+ * sources share their offset from a 16-byte boundary (head and tail bytewise), bytes otherwise.
+ * Row bases are 64-bit.  EINVAL before any launch: den outside 1..4096, nbytes < 1, n0 outside
+ * 1..65535, n_rows outside 0..65535, n outside 0..den-1, lo outside -1..n_slots-1, hi outside the
+ * slots of a row that blends, pair < -1, and with cut: pair >= n_pairs or hold outside the slots;
+ * overlapping strides; null pointers.  n_rows == 0 launches nothing.
+ */
+typedef struct dvie_synth_retime_desc {
+  const uint8_t* slots;
+  uint8_t* out;
+  const int32_t* rows;     /* host */
+  const int32_t* rows_dev; /* device */
+  const uint8_t* cut;      /* device, may be NULL */
+  long long slot_s0, slot_s1, out_s0, out_s1; /* byte strides of (clip, slot) and (clip, row) */
+  long long nbytes;                           /* bytes of a slot and of a row */
+  int n0, n_slots, n_rows, n_pairs, den, pad0;
+} dvie_synth_retime_desc;
+
+int dvie_synth_retime(const dvie_synth_retime_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* The pairs of ops dvie_run_ops(ops, n) runs as chained launches (host only, nothing is
@@ -1269,7 +1308,7 @@ int dvie_ops_chain_pairs(const dvie_op* ops, int n, int* partner);
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
  * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim, synth_yuv,
- * synth_scene, synth_cutfill, synth_tile_blend). */
+ * synth_scene, synth_cutfill, synth_tile_blend; 116 is unused and answers 0; 117: synth_retime). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);
