@@ -222,6 +222,21 @@ class SynthRetimeDesc(ctypes.Structure):
     ]
 
 
+class SynthFlipDesc(ctypes.Structure):
+    _fields_ = [
+        ("src", vp), ("dst", vp), ("lsrc", vp), ("ldst", vp), ("src_stride", i64), ("lsrc_stride", i64),
+        ("n", i32), ("h", i32), ("w", i32), ("ld", i32),
+    ]
+
+
+class SynthEnsAccDesc(ctypes.Structure):
+    _fields_ = [
+        ("rgb", vp), ("seg", vp), ("rgb_acc", vp), ("seg_acc", vp),
+        ("n", i32), ("h", i32), ("w", i32), ("rgb_ld", i32), ("seg_ld", i32), ("n_classes", i32),
+        ("flip", i32), ("first", i32), ("last_m", i32), ("pad0", i32),
+    ]
+
+
 TILE_MAX = 32  # DVIE_TILE_MAX: tiles per axis of dvie_synth_tile_blend
 
 
@@ -352,7 +367,8 @@ _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, 
         108: SynthLoadPadDesc, 109: SynthFinishCropDesc, 110: SynthVggLoadDesc}
 # descriptors added after the set tests/test_perceptual_cpu.py pins for _ABI; load() checks both tables
 _ABI_MORE = {111: SynthMsssimDesc, 112: SynthYuvDesc, 113: SynthSceneDesc, 114: SynthCutFillDesc,
-             115: SynthTileBlendDesc, 117: SynthRetimeDesc}  # (116 is unused and answers 0)
+             115: SynthTileBlendDesc, 117: SynthRetimeDesc,  # (116 is unused and answers 0)
+             118: SynthFlipDesc, 119: SynthEnsAccDesc}
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -368,7 +384,7 @@ EXPORTS = [
     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks", "dvie_synth_msssim", "dvie_synth_msssim_ws_bytes",
     "dvie_synth_yuv2rgb", "dvie_synth_rgb2yuv", "dvie_conv_chain", "dvie_conv2d_chain", "dvie_ops_chain_pairs",
     "dvie_synth_scene", "dvie_synth_scene_ws_bytes", "dvie_synth_cutfill", "dvie_synth_tile_blend",
-    "dvie_synth_retime",
+    "dvie_synth_retime", "dvie_synth_flip", "dvie_synth_ens_acc",
 ]
 
 _lib = None
@@ -407,7 +423,7 @@ def load():
                      "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop",
                      "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_synth_msssim", "dvie_synth_yuv2rgb",
                      "dvie_synth_rgb2yuv", "dvie_synth_scene", "dvie_synth_cutfill", "dvie_synth_tile_blend",
-                     "dvie_synth_retime"):
+                     "dvie_synth_retime", "dvie_synth_flip", "dvie_synth_ens_acc"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]

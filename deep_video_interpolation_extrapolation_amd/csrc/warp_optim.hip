@@ -886,6 +886,8 @@ size_t dvie_abi_sizeof(int which) {
     case 114: return sizeof(dvie_synth_cutfill_desc);
     case 115: return sizeof(dvie_synth_tile_blend_desc);
     case 117: return sizeof(dvie_synth_retime_desc);  // (116 stays 0: tests/test_tile_cpu.py pins it as unused)
+    case 118: return sizeof(dvie_synth_flip_desc);
+    case 119: return sizeof(dvie_synth_ens_acc_desc);
     default: return 0;
   }
 }

@@ -81,6 +81,16 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
                             an input interval); `blend` cross-fades the two neighbouring grid frames, which
                             are 1/2**K of an input interval apart, with exact integer rounding.  Neither
                             has been judged on trained weights and real footage
+  --synth_ensemble {none,time,flip,time+flip}
+                            --split test (also with --synth_eval): test-time self-ensembling
+                            (synth.VideoSynthesizer(ensemble=)).  Every predicted frame is the fp32 mean of
+                            M forwards: `time` (M = 2) adds the forward with the two input frames in
+                            exchanged roles, `flip` (M = 2) the forward on the horizontally mirrored inputs,
+                            mirrored back, `time+flip` (M = 4) all four; the label is the argmax of the mean
+                            logits.  One log line per run names the ensemble and M.  EXTRA takes only
+                            `flip`: extrapolation has no time symmetry, and `time` ends the run.  Default
+                            `none`; whether the M-fold cost pays off on given weights is what --synth_eval
+                            with and without the flag tells -- it has not been measured on trained weights
 """
 import argparse
 
@@ -202,6 +212,7 @@ GLOBAL = [
     ("--synth_tile_overlap", "synth_tile_overlap", _overlap, 64, None),
     ("--synth_rate", "synth_rate", _rate, None, None),
     ("--synth_rate_mode", "synth_rate_mode", str, "nearest", ["nearest", "blend"]),
+    ("--synth_ensemble", "synth_ensemble", str, "none", ["none", "time", "flip", "time+flip"]),
 ]
 
 # second-stage flags of the reference's INTER sub-command (options/options.py:296-380);

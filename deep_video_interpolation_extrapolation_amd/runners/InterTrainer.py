@@ -351,12 +351,18 @@ class InterTrainer:
     def _synthesizer(self):
         """--split test: the VideoSynthesizer of this run (--bs pairs per forward, --synth_pad,
         --synth_tile and --synth_tile_overlap; a tile that is no multiple of the net's stride is
-        the constructor's ValueError, which names that multiple)"""
+        the constructor's ValueError, which names that multiple; --synth_ensemble, logged once per
+        run when it is on: `time` on an extrapolation net is the constructor's ValueError too)"""
         from ..synth import VideoSynthesizer
         pad = getattr(self.args, "synth_pad", "none")
-        return VideoSynthesizer(self.model.module, max_batch=max(1, self.args.batch_size),
-                                pad=None if pad == "none" else pad, tile=getattr(self.args, "synth_tile", None),
-                                overlap=getattr(self.args, "synth_tile_overlap", 64))
+        ens = getattr(self.args, "synth_ensemble", "none")
+        syn = VideoSynthesizer(self.model.module, max_batch=max(1, self.args.batch_size),
+                               pad=None if pad == "none" else pad, tile=getattr(self.args, "synth_tile", None),
+                               overlap=getattr(self.args, "synth_tile_overlap", 64),
+                               ensemble=None if ens == "none" else ens)
+        if syn.ensemble is not None:
+            self.log.info("synth: self-ensemble {}: {} forwards per predicted frame".format(ens, len(syn.members)))
+        return syn
 
     @staticmethod
     def _size_hint(e):
@@ -699,7 +705,8 @@ class InterTrainer:
         With --synth_msssim K every scored frame also gets its K-scale MS-SSIM (synth.frame_msssim):
         "msssim" per clip, in the summary and in every per_position row, and a top-level
         "msssim_scales"; a clip too small for K scales ends the run with a ValueError naming the
-        clip (K is never reduced: one scores.json holds one metric)."""
+        clip (K is never reduced: one scores.json holds one metric).  With --synth_ensemble other than
+        `none` the synthesis is the ensemble's and a top-level "ensemble" names it."""
         import numpy as np
         from PIL import Image
         from ..synth import PerceptualScorer, msssim_check, summarize, vgg_region
@@ -748,6 +755,8 @@ class InterTrainer:
             res["vgg_weights"] = scorer.weights_name
         if scales:
             res["msssim_scales"] = scales
+        if syn.ensemble is not None:
+            res["ensemble"] = syn.ensemble
         root = os.path.join(a.cycgen_load_dir, "synth_eval")
         os.makedirs(root, exist_ok=True)
         with open(os.path.join(root, "scores.json"), "w") as f:

@@ -67,6 +67,12 @@ the midpoint tree to the forwards those slots need and numbers the surviving slo
 unchanged `_roll` runs that schedule, and `retime_gather` (dvie_synth_retime) copies or blends the
 slots into the output frames in one launch, holding frames across flagged pairs from the flags on
 the device.
+
+Self-ensemble (opt-in, `ensemble=`): inside one forward (`_run`) the net runs once per member of
+`ensemble_members` -- the two inputs in exchanged roles, mirrored along W (`dvie_synth_flip`), or
+both -- and `dvie_synth_ens_acc` sums the members' raw images and coarse logits, mirrored back, into
+their fp32 means in place, so the finish, the tile stash and every layer above read the means as they
+read a single forward's outputs.
 """
 import ctypes
 
@@ -193,6 +199,59 @@ def synth_finish_crop(rgb, seg, frame, label, label_canvas=None, n_classes=20):
         assert label_canvas.dtype == torch.uint8 and label_canvas.is_contiguous() and label_canvas.shape == rgb.shape[:3]
         d.label_canvas = label_canvas.data_ptr()
     L.check(L.load().dvie_synth_finish_crop(ctypes.byref(d), L.stream_ptr(rgb.device)), "synth finish_crop")
+
+
+ENSEMBLES = (None, "time", "flip", "time+flip")
+
+
+def ensemble_members(ensemble):
+    """The members (swap, flip) of a self-ensemble, in the order their outputs are summed.  swap:
+    the two input frames and their label maps exchange roles (the midpoint of (a, b) is the midpoint
+    of (b, a)); flip: the four inputs are mirrored along W and the member's outputs mirrored back.
+    None: [(0, 0)], the plain forward.  Anything else: ValueError naming the choices."""
+    if ensemble is None:
+        return [(0, 0)]
+    table = {"time": [(0, 0), (1, 0)], "flip": [(0, 0), (0, 1)], "time+flip": [(0, 0), (1, 0), (0, 1), (1, 1)]}
+    if not isinstance(ensemble, str) or ensemble not in table:
+        raise ValueError(f'ensemble must be None, "time", "flip" or "time+flip", got {ensemble!r}')
+    return list(table[ensemble])
+
+
+def synth_flip(src, lsrc, dst, ldst):
+    """The W-mirror of one input of a forward (dvie_synth_flip, one launch): fp32 `src` (n, H, W, ld),
+    its images contiguous and strided over n -> contiguous `dst`; uint8 label maps `lsrc` (n, H, W),
+    strided over n -> contiguous `ldst` (lsrc and ldst both or neither None)."""
+    L.require_gpu(src)
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and src.dim() == 4 and dst.shape == src.shape
+    n, H, W, ld = src.shape
+    assert dst.is_contiguous() and src.stride()[1:] == (W * ld, ld, 1), (src.shape, src.stride())
+    d = L.SynthFlipDesc()
+    d.src, d.dst, d.src_stride = src.data_ptr(), dst.data_ptr(), src.stride(0)
+    d.n, d.h, d.w, d.ld = n, H, W, ld
+    if lsrc is not None or ldst is not None:
+        assert lsrc.dtype == torch.uint8 and ldst.dtype == torch.uint8 and tuple(lsrc.shape) == tuple(ldst.shape) == (n, H, W)
+        assert ldst.is_contiguous() and lsrc.stride()[1:] == (W, 1), (lsrc.shape, lsrc.stride())
+        d.lsrc, d.ldst, d.lsrc_stride = lsrc.data_ptr(), ldst.data_ptr(), lsrc.stride(0)
+    L.check(L.load().dvie_synth_flip(ctypes.byref(d), L.stream_ptr(src.device)), "synth flip")
+    return dst
+
+
+def synth_ens_acc(rgb, seg, rgb_acc, seg_acc, flip=False, first=False, last_m=0, n_classes=20):
+    """One ensemble member's raw image `rgb` (n, H, W, rgb_ld) and coarse logits `seg` (n, H, W,
+    seg_ld) into the accumulators of the same shapes (dvie_synth_ens_acc, one launch; all fp32 and
+    contiguous): acc = member (first) or acc + member, the member read at the mirrored column with
+    flip, then times 1 / last_m when last_m is 2 or 4; the padding channels are written as 0."""
+    L.require_gpu(rgb)
+    for t, a in ((rgb, rgb_acc), (seg, seg_acc)):
+        assert t.dtype == torch.float32 and a.dtype == torch.float32 and t.is_contiguous() and a.is_contiguous()
+        assert t.dim() == 4 and t.shape == a.shape, (t.shape, a.shape)
+    assert rgb.shape[:3] == seg.shape[:3], (rgb.shape, seg.shape)
+    d = L.SynthEnsAccDesc()
+    d.rgb, d.seg, d.rgb_acc, d.seg_acc = rgb.data_ptr(), seg.data_ptr(), rgb_acc.data_ptr(), seg_acc.data_ptr()
+    d.n, d.h, d.w, d.rgb_ld = rgb.shape
+    d.seg_ld, d.n_classes = seg.shape[3], n_classes
+    d.flip, d.first, d.last_m = int(bool(flip)), int(bool(first)), int(last_m)
+    L.check(L.load().dvie_synth_ens_acc(ctypes.byref(d), L.stream_ptr(rgb.device)), "synth ens_acc")
 
 
 TILE_MAX = L.TILE_MAX  # tiles per axis
@@ -1098,8 +1157,9 @@ class FrameSizeError(ValueError):
 
 
 class _Captured:
-    """One forward (every stage of it) + finish of a fixed (n, H, W) as a hipGraph over static
-    tensors.  With a padded canvas (H, W) is the canvas and `crop` the (h, w) of the frames that
+    """One forward (every stage of it; with an ensemble every member's, with the flips and the
+    accumulates between them) + finish of a fixed (n, H, W) as a hipGraph over static tensors: one
+    single-stream chain either way.  With a padded canvas (H, W) is the canvas and `crop` the (h, w) of the frames that
     leave: the static frame and label have the cropped size, and the label canvas is static too."""
 
     def __init__(self, syn, n, H, W, dev, crop=None):
@@ -1162,9 +1222,17 @@ class VideoSynthesizer:
     canvas that fits one tile runs exactly as with tile=None.  A tiled frame approximates the
     untiled one: the net's receptive field is wider than any overlap, and a tile's inner borders
     see zero padding.  A forward of more than `max_pixels` pixels raises FrameSizeError before
-    anything is launched."""
+    anything is launched.
+    ensemble: None -- one forward per prediction; "time", "flip" or "time+flip" -- test-time
+    self-ensembling: every forward runs once per member of ensemble_members(ensemble) (the inputs
+    in exchanged roles, mirrored along W over the extent the forward runs on -- the canvas, the
+    tile -- or both), the mirrored outputs are mirrored back, and the raw image and the coarse
+    logits become the fp32 means (((x0 + x1) + x2) + x3) * (1 / M); the frame, the label and what
+    later levels read come from the means.  M forwards per predicted frame.  An Extra net takes
+    only "flip" (ValueError: extrapolation has no time symmetry).  Its effect on quality has not
+    been measured on trained weights."""
 
-    def __init__(self, net, max_batch=8, graph=False, pad=None, tile=None, overlap=64):
+    def __init__(self, net, max_batch=8, graph=False, pad=None, tile=None, overlap=64, ensemble=None):
         from .nets.ExtraNet import ExtraNet, ExtraRefineNet, ExtraStage3Net
         from .nets.HRNet import HRNet
         from .nets.InterNet import InterNet
@@ -1188,6 +1256,11 @@ class VideoSynthesizer:
         if pad not in (None, "replicate"):
             raise ValueError(f'pad must be None or "replicate", got {pad!r}')
         self.pad = pad
+        self.members = ensemble_members(ensemble)  # (ValueError for an unknown setting)
+        if any(swap for swap, _ in self.members) and isinstance(net, (ExtraNet, ExtraRefineNet, ExtraStage3Net)):
+            raise ValueError(f'ensemble={ensemble!r}: extrapolation has no time symmetry (the frame after (a, b) is not '
+                             f'the frame after (b, a)); an Extra net takes ensemble=None or "flip"')
+        self.ensemble = ensemble
         net.eval()
         self.net, self.cm, self.max_batch, self.graph = net, cm, int(max_batch), bool(graph)
         self._scratch = {}  # (n, H, W, device) -> the scratch tensors of a forward
@@ -1295,16 +1368,61 @@ class VideoSynthesizer:
             if self.stages:
                 sc["stem"] = torch.empty((n, 7 * self.cm.n_frames, H, W), **f32)
                 sc["img"] = [torch.empty((n, H, W, 8), **f32) for _ in self.stages]
+            if self.ensemble is not None:
+                # a later member's raw image and logits (32 + 96 B per pixel and pair) and, for a
+                # mirrored member, the mirrors of the four inputs (2 * 32 + 2 B)
+                sc["ens_rgb"], sc["ens_seg"] = torch.empty((n, H, W, 8), **f32), torch.empty_like(sc["seg"])
+                if any(flip for _, flip in self.members):
+                    u8 = dict(dtype=torch.uint8, device=dev)
+                    sc["ens_x"] = [torch.empty((n, H, W, 8), **f32) for _ in range(2)]
+                    sc["ens_l"] = [torch.empty((n, H, W), **u8) for _ in range(2)]
             self._scratch[key] = sc
         return self._scratch[key]
 
     def _run(self, plans, xa, xb, la, lb, rgb, frame, label, lcan=None):
         """rgb (fp32, raw), frame, label <- net(xa, xb | la, lb); every tensor a contiguous
         (n, H, W, ...) block (the inputs may be strided over n).  On a padded canvas frame and
-        label are (n, h, w, ...), the crop, and lcan (or None) gets the label canvas (n, H, W)."""
+        label are (n, h, w, ...), the crop, and lcan (or None) gets the label canvas (n, H, W).
+        With an ensemble rgb and the coarse logits are the members' means (_run_members)."""
         n, H, W, _ = rgb.shape
         sc = self._scratch_of(n, H, W, rgb.device)
         seg = sc["seg"]
+        if self.ensemble is None:
+            self._forward(plans, sc, xa, xb, la, lb, rgb, seg)
+        else:
+            self._run_members(plans, sc, xa, xb, la, lb, rgb, seg)
+        if frame is None:  # (a tile of a tiled forward: tile_blend finishes the canvas)
+            return
+        if frame.shape[1:3] == (H, W):
+            synth_finish(rgb, seg, frame, label, n_classes=self.cm.n_classes)
+        else:
+            synth_finish_crop(rgb, seg, frame, label, lcan, n_classes=self.cm.n_classes)
+
+    def _run_members(self, plans, sc, xa, xb, la, lb, rgb, seg):
+        """The members of the ensemble in order, each a complete forward (its bridges read its own
+        coarse image and logits): a swapped member reads the inputs in exchanged roles, a mirrored
+        one their synth_flip copies.  Member 0, the plain forward, writes rgb and seg themselves;
+        every later one writes the ens_* scratch and synth_ens_acc adds it (read mirrored back),
+        the last one scaling by 1 / M and zeroing the padding channels: rgb and seg end as
+        (((x0 + x1) + x2) + x3) * (1 / M)."""
+        M = len(self.members)
+        for m, (swap, flip) in enumerate(self.members):
+            a, b, sa, sb = (xb, xa, lb, la) if swap else (xa, xb, la, lb)
+            if flip:
+                (fa, fb), (fla, flb) = sc["ens_x"], sc["ens_l"]
+                a, sa = synth_flip(a, sa, fa, fla), fla
+                b, sb = synth_flip(b, sb, fb, flb), flb
+            if m == 0:
+                assert not swap and not flip
+                self._forward(plans, sc, a, b, sa, sb, rgb, seg)
+                continue
+            self._forward(plans, sc, a, b, sa, sb, sc["ens_rgb"], sc["ens_seg"])
+            synth_ens_acc(sc["ens_rgb"], sc["ens_seg"], rgb, seg, flip=flip, last_m=M if m == M - 1 else 0,
+                          n_classes=self.cm.n_classes)
+
+    def _forward(self, plans, sc, xa, xb, la, lb, rgb, seg):
+        """one forward of every stage: the raw image of the last stage into rgb, the coarse logits
+        into seg"""
         imgs = sc.get("img", []) + [rgb]  # the image each plan writes: the last one is the prediction
         xs = [xa.permute(0, 3, 1, 2)[:, :3], xb.permute(0, 3, 1, 2)[:, :3]]
         plan = plans[0]
@@ -1328,12 +1446,6 @@ class VideoSynthesizer:
                 plan.set_input_labels("nseg", [la, lb])
                 plan.set_output_nchw("out", imgs[k + 1].permute(0, 3, 1, 2))
             plan.run_forward()
-        if frame is None:  # (a tile of a tiled forward: tile_blend finishes the canvas)
-            return
-        if frame.shape[1:3] == (H, W):
-            synth_finish(rgb, seg, frame, label, n_classes=self.cm.n_classes)
-        else:
-            synth_finish_crop(rgb, seg, frame, label, lcan, n_classes=self.cm.n_classes)
 
     def _tile_scratch_of(self, n, th, tw, nt, dev):
         """the reused scratch of a tiled forward of n pairs: the tile crops of the four inputs, the

@@ -1292,6 +1292,70 @@ typedef struct dvie_synth_retime_desc {
 
 int dvie_synth_retime(const dvie_synth_retime_desc* d, void* stream);
 
+/*
+ * dvie_synth_flip: the W-mirror of one input of a forward -- a frame's fp32 form and its label map
+ * -- for a mirrored member of a self-ensemble (synth.synth_flip; DESIGN.md "Self-ensemble").  One
+ * launch for both.
+ *
+ *   dst[i, y, x, c]  = src[i, y, w-1-x, c]     fp32, c in 0..ld-1 (every channel, bit for bit)
+ *   ldst[i, y, x]    = lsrc[i, y, w-1-x]       uint8, when lsrc and ldst are given (both or neither)
+ *
+ * src is n images of (h, w, ld) floats, each contiguous, image i at src + i*src_stride FLOATS; lsrc
+ * n label maps of (h, w) bytes, map i at lsrc + i*lsrc_stride BYTES; dst (n, h, w, ld) and ldst
+ * (n, h, w) are contiguous.  src, dst and src_stride are 16-byte aligned (ld % 4 == 0): a lane moves
+ * one 16-byte vector of a pixel.  The label maps need no alignment: a group of 4 bytes whose source
+ * and destination both sit on a dword boundary is one byte-reversed dword, every other byte (row
+ * tails, rows with an unaligned base) moves on its own.  Every output byte has one owning lane; no
+ * byte outside dst and ldst is written.  EINVAL before any launch: null src / dst, lsrc without
+ * ldst or the reverse, n, h or w < 1, ld no positive multiple of 4, a stride smaller than an image
+ * (n > 1) or src_stride % 4 != 0, unaligned src / dst, src == dst or lsrc == ldst (the mirror is not
+ * done in place), a source range that overlaps its destination.  All offsets are 64-bit.
+ */
+typedef struct dvie_synth_flip_desc {
+  const float* src;
+  float* dst;
+  const uint8_t* lsrc; /* may be NULL (then ldst is NULL too) */
+  uint8_t* ldst;
+  long long src_stride;  /* floats between images of src */
+  long long lsrc_stride; /* bytes between maps of lsrc */
+  int n, h, w, ld;
+} dvie_synth_flip_desc;
+
+int dvie_synth_flip(const dvie_synth_flip_desc* d, void* stream);
+
+/*
+ * dvie_synth_ens_acc: one member of a self-ensemble added to the running sums of the raw image and
+ * of the coarse logits (synth.synth_ens_acc; DESIGN.md "Self-ensemble").  One launch.
+ *
+ * rgb (n, h, w, rgb_ld) and seg (n, h, w, seg_ld) are the member's outputs, rgb_acc and seg_acc the
+ * accumulators of the same shapes; all fp32, contiguous, 16-byte aligned and disjoint.  With
+ * xs = w-1-x when flip is set and xs = x otherwise, per pixel (i, y, x), for the channels c in 0..2
+ * of the image and the classes c in 0..n_classes-1 of the logits, in fp32:
+ *   m = member[i, y, xs, c]
+ *   a = first ? m : acc[i, y, x, c] + m
+ *   acc[i, y, x, c] = last_m ? a * (1.f / last_m) : a
+ * The add and the multiply are two roundings, as written; last_m is 0, 2 or 4, so 1.f / last_m is
+ * exact.  Channels 3..rgb_ld-1 of rgb_acc and classes n_classes..seg_ld-1 of seg_acc are written
+ * as 0.f by every call.  A chain of M members in order -- the first with `first`, the last with
+ * last_m = M -- therefore leaves (((x0 + x1) + x2) + x3) * (1/M).  (The first member may as well be
+ * written into the accumulators by its forward: the sums are the same bits, and the last call
+ * zeroes the padding.)  Every output vector has one owning lane, which is also the only reader of
+ * that accumulator vector.  EINVAL before any launch: null pointers, n, h or w < 1, a leading
+ * dimension that is no positive multiple of 4, n_classes outside 1..seg_ld, last_m outside
+ * {0, 2, 4}, flip or first outside {0, 1}, unaligned or overlapping buffers.  All offsets are 64-bit.
+ */
+typedef struct dvie_synth_ens_acc_desc {
+  const float* rgb;
+  const float* seg;
+  float* rgb_acc;
+  float* seg_acc;
+  int n, h, w;
+  int rgb_ld, seg_ld, n_classes;
+  int flip, first, last_m, pad0;
+} dvie_synth_ens_acc_desc;
+
+int dvie_synth_ens_acc(const dvie_synth_ens_acc_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* The pairs of ops dvie_run_ops(ops, n) runs as chained launches (host only, nothing is
@@ -1308,7 +1372,8 @@ int dvie_ops_chain_pairs(const dvie_op* ops, int n, int* partner);
 /* ABI self-check: sizeof of each descriptor, indexed by DVIE_OP_* (0 = dvie_op; 100.. the
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
  * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim, synth_yuv,
- * synth_scene, synth_cutfill, synth_tile_blend; 116 is unused and answers 0; 117: synth_retime). */
+ * synth_scene, synth_cutfill, synth_tile_blend; 116 is unused and answers 0; 117: synth_retime,
+ * 118: synth_flip, 119: synth_ens_acc). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

@@ -68,8 +68,14 @@
   and PSNR / mean absolute difference of the tiled against the untiled uint8 frame at 1080x1920,
   inside and outside the overlap bands (information only).
 
+* the self-ensemble (--ensemble): ms per VideoSynthesizer.interpolate call (one forward of the pairs,
+  levels=1, bf16 coarse InterNet, random weights) at 8x256x512 and 1x1080x1920 for ensemble=None,
+  "time", "flip" and "time+flip", the legs alternating in one process, three rounds, median and
+  range, with the ratio to None; and us per launch and TB/s of dvie_synth_flip and
+  dvie_synth_ens_acc alone over buffer sets that exceed the Infinity Cache.
+
     python tools/synth_bench.py [--seconds 1.0] [--steps 8] [--json out.json]
-                                [--two-stage | --score | --pad | --vgg | --msssim | --yuv | --scene | --tile]
+                                [--two-stage | --score | --pad | --vgg | --msssim | --yuv | --scene | --tile | --ensemble]
 """
 import argparse
 import json
@@ -87,7 +93,7 @@ from deep_video_interpolation_extrapolation_amd.runners.InterTrainer import Inte
 from deep_video_interpolation_extrapolation_amd import losses  # noqa: E402
 from deep_video_interpolation_extrapolation_amd.synth import (VideoSynthesizer, frame_scores, synth_bridge,  # noqa: E402
                                                               frame_msssim, synth_finish, synth_finish_crop,
-                                                              synth_load, synth_load_pad)
+                                                              synth_load, synth_load_pad, synth_flip, synth_ens_acc)
 
 
 def make_net(large=False):
@@ -871,6 +877,63 @@ def interpolate_numbers(dev, seconds):
     return {k: dict(frames_per_s=sorted(v)[1], runs=v) for k, v in rates.items()}
 
 
+ENSEMBLE_SHAPES = ((8, 256, 512), (1, 1080, 1920))  # (clips = pairs per forward, H, W)
+
+
+def ensemble_numbers(dev, seconds):
+    """the self-ensemble: ms per interpolate() call (one forward of n pairs, levels=1, bf16 coarse
+    InterNet, random weights; pad="replicate", which 1080x1920 does not need at the coarse net's
+    multiple of 4) for ensemble=None,
+    "time", "flip" and "time+flip", alternating in one process, three rounds, median (min - max), with
+    the ratio to None; and us per launch and TB/s of algorithmic bytes of dvie_synth_flip (one frame
+    and its label map, 33 B read and written per pixel) and dvie_synth_ens_acc (a mirrored member
+    added and scaled: the 6 live vectors of member and sums, 2 x 96 B, read and 128 B written per pixel) alone, rotating over buffer sets that
+    exceed the Infinity Cache"""
+    net = make_inter_net().to(dev).eval()
+    out = {}
+    for n, H, W in ENSEMBLE_SHAPES:
+        frames = torch.randint(0, 256, (n, 2, H, W, 3), dtype=torch.uint8, device=dev)
+        labels = torch.randint(0, 20, (n, 2, H, W), dtype=torch.uint8, device=dev)
+        legs = {}
+        for setting in (None, "time", "flip", "time+flip"):
+            syn = VideoSynthesizer(net, max_batch=n, pad="replicate", ensemble=setting)
+            legs[str(setting).lower()] = lambda syn=syn: syn.interpolate(frames, labels, 1)
+        rates = _alternate(legs, seconds)
+        row = {k: dict(ms=1e3 / sorted(v)[1], min_ms=1e3 / max(v), max_ms=1e3 / min(v)) for k, v in rates.items()}
+        for k in legs:
+            row[k]["over_none"] = row[k]["ms"] / row["none"]["ms"]
+        Hp, Wp = -(-H // 4) * 4, -(-W // 4) * 4
+        npix = n * Hp * Wp
+        sets = (320 << 20) // (160 * npix) + 2
+        f32 = dict(dtype=torch.float32, device=dev)
+        src = [torch.randn((n, Hp, Wp, 8), **f32) for _ in range(sets)]
+        lsrc = [torch.randint(0, 20, (n, Hp, Wp), dtype=torch.uint8, device=dev) for _ in range(sets)]
+        dst, ldst = torch.empty_like(src[0]), torch.empty_like(lsrc[0])
+        seg = [torch.randn((n, Hp, Wp, 24), **f32) for _ in range(sets)]
+        acc_r = [torch.randn((n, Hp, Wp, 8), **f32) for _ in range(sets)]
+        acc_s = [torch.randn((n, Hp, Wp, 24), **f32) for _ in range(sets)]
+        k = [0]
+
+        def flip():
+            i = k[0] = (k[0] + 1) % sets
+            synth_flip(src[i], lsrc[i], dst, ldst)
+
+        def acc():
+            i = k[0] = (k[0] + 1) % sets
+            synth_ens_acc(src[i], seg[i], acc_r[i], acc_s[i], flip=True, last_m=2)
+
+        kr = _alternate(dict(flip=flip, ens_acc=acc), seconds)
+        for name, nbytes in (("flip", 2 * 33), ("ens_acc", 2 * 96 + 128)):
+            v = kr[name]
+            row[f"{name}_kernel"] = dict(us=1e6 / sorted(v)[1], min_us=1e6 / max(v), max_us=1e6 / min(v),
+                                         tb_per_s=npix * nbytes * sorted(v)[1] / 1e12, buffer_sets=sets)
+        row["scratch_bytes"] = npix * (2 * 32 + 2 + 128)
+        out[f"{n}x{H}x{W}"] = row
+        del src, lsrc, seg, acc_r, acc_s, frames, labels, legs
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=1.0)
@@ -886,7 +949,15 @@ def main():
     ap.add_argument("--yuv", action="store_true", help="only the colour-conversion legs")
     ap.add_argument("--scene", action="store_true", help="only the scene-cut legs")
     ap.add_argument("--tile", action="store_true", help="only the tiled-synthesis legs")
+    ap.add_argument("--ensemble", action="store_true", help="only the self-ensemble legs")
     a = ap.parse_args()
+    if a.ensemble:
+        res = dict(ensemble_interpolate_bf16=ensemble_numbers(torch.device("cuda:0"), a.seconds))
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.tile:
         dev = torch.device("cuda:0")
         res = dict(tile_blend_2160x3840=tile_blend_numbers(dev, a.seconds))
