@@ -237,6 +237,16 @@ class SynthEnsAccDesc(ctypes.Structure):
     ]
 
 
+class SynthMotionDesc(ctypes.Structure):
+    _fields_ = [
+        ("cur", vp), ("ref", vp), ("d2", vp), ("sad", vp), ("sad0", vp), ("border", vp), ("mv", vp), ("bsad", vp),
+        ("ws", vp),
+        ("cur_s0", i64), ("cur_s1", i64), ("ref_s0", i64), ("ref_s1", i64),
+        ("n0", i32), ("n1", i32), ("h", i32), ("w", i32),
+        ("radius", i32), ("scale", i32), ("penalty", i32), ("pad0", i32),
+    ]
+
+
 TILE_MAX = 32  # DVIE_TILE_MAX: tiles per axis of dvie_synth_tile_blend
 
 
@@ -368,7 +378,8 @@ _ABI = {0: Op, OP_CONV: ConvDesc, OP_WGRAD: WgradDesc, OP_WREDUCE: WreduceDesc, 
 # descriptors added after the set tests/test_perceptual_cpu.py pins for _ABI; load() checks both tables
 _ABI_MORE = {111: SynthMsssimDesc, 112: SynthYuvDesc, 113: SynthSceneDesc, 114: SynthCutFillDesc,
              115: SynthTileBlendDesc, 117: SynthRetimeDesc,  # (116 is unused and answers 0)
-             118: SynthFlipDesc, 119: SynthEnsAccDesc}
+             118: SynthFlipDesc, 119: SynthEnsAccDesc,
+             121: SynthMotionDesc}  # (120 is unused and answers 0)
 
 EXPORTS = [
     "dvie_conv2d_fwd", "dvie_conv2d_wgrad", "dvie_wgrad_splits_hint", "dvie_wgrad_slabs", "dvie_wgrad_reduce", "dvie_wgrad_reduce_multi", "dvie_colsum", "dvie_pack_weights",
@@ -384,7 +395,7 @@ EXPORTS = [
     "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_cosfeat_blocks", "dvie_synth_msssim", "dvie_synth_msssim_ws_bytes",
     "dvie_synth_yuv2rgb", "dvie_synth_rgb2yuv", "dvie_conv_chain", "dvie_conv2d_chain", "dvie_ops_chain_pairs",
     "dvie_synth_scene", "dvie_synth_scene_ws_bytes", "dvie_synth_cutfill", "dvie_synth_tile_blend",
-    "dvie_synth_retime", "dvie_synth_flip", "dvie_synth_ens_acc",
+    "dvie_synth_retime", "dvie_synth_flip", "dvie_synth_ens_acc", "dvie_synth_motion", "dvie_synth_motion_ws_bytes",
 ]
 
 _lib = None
@@ -423,7 +434,7 @@ def load():
                      "dvie_synth_bridge", "dvie_synth_score", "dvie_synth_load_pad", "dvie_synth_finish_crop",
                      "dvie_synth_vgg_load", "dvie_cosfeat", "dvie_synth_msssim", "dvie_synth_yuv2rgb",
                      "dvie_synth_rgb2yuv", "dvie_synth_scene", "dvie_synth_cutfill", "dvie_synth_tile_blend",
-                     "dvie_synth_retime", "dvie_synth_flip", "dvie_synth_ens_acc"):
+                     "dvie_synth_retime", "dvie_synth_flip", "dvie_synth_ens_acc", "dvie_synth_motion"):
             getattr(lib, name).argtypes = [vp, vp]
             getattr(lib, name).restype = i32
         lib.dvie_pack_weights.argtypes = [vp, i32, i32, vp]
@@ -458,6 +469,8 @@ def load():
         lib.dvie_synth_msssim_ws_bytes.restype = ctypes.c_size_t
         lib.dvie_synth_scene_ws_bytes.argtypes = [vp]
         lib.dvie_synth_scene_ws_bytes.restype = ctypes.c_size_t
+        lib.dvie_synth_motion_ws_bytes.argtypes = [vp]
+        lib.dvie_synth_motion_ws_bytes.restype = ctypes.c_size_t
         lib.dvie_adamax.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]
         lib.dvie_scale.argtypes = [vp, i64, f32, vp]
         lib.dvie_adam.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]

@@ -888,6 +888,7 @@ size_t dvie_abi_sizeof(int which) {
     case 117: return sizeof(dvie_synth_retime_desc);  // (116 stays 0: tests/test_tile_cpu.py pins it as unused)
     case 118: return sizeof(dvie_synth_flip_desc);
     case 119: return sizeof(dvie_synth_ens_acc_desc);
+    case 121: return sizeof(dvie_synth_motion_desc);  // (120 stays 0: tests/test_ensemble_cpu.py pins it as unused)
     default: return 0;
   }
 }

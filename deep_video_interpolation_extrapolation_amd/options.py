@@ -23,6 +23,23 @@ Same flags / dests / defaults for the global options and the EXTRA and INTER sub
   --synth_msssim K          with --synth_eval: also the per-frame K-scale MS-SSIM (synth.frame_msssim,
                             1 <= K <= 5; 0 = off) -> "msssim" per clip and in the summary of scores.json,
                             and "msssim_scales"; a clip with min(H, W) >> (K - 1) < 11 ends the run
+  --synth_motion            with --synth_eval: also block-matching motion statistics (synth.block_motion,
+                            synth.MotionSearch) -> per clip and slot "motion" (the RMS block displacement
+                            between the two input frames that bracket the slot, pixels per input
+                            interval), "motion_saturated" (the fraction of their blocks whose vector lies
+                            on the border of the search), "tres" and "tres_gt" (the motion-compensated
+                            residual across the slot in the synthesised and in the original video, grey
+                            levels per sample); the summary and its per_position rows gain their means
+                            and "tres_excess" = mean(tres - tres_gt), and a "per_motion" table groups
+                            the frames by "motion" at --synth_motion_edges; a top-level "motion" names
+                            the search.  A clip whose mean saturation exceeds one half is logged once
+  --synth_motion_radius R   the search radius in plane samples, 1..32 (default 16)
+  --synth_motion_scale S    match on the luma averaged over 2**S x 2**S pixels, 0..3 (default 0): a
+                            radius of R then reaches R * 2**S frame pixels
+  --synth_motion_edges a,b,c
+                            the ascending positive bucket edges of per_motion (default 2,8,32).  The
+                            defaults of all three are provisional: they have not been validated on real
+                            footage
   --synth_pad {none,replicate}
                             --split test: `none` takes only clips whose height and width are multiples
                             of the net's coarsest stride (4; 8 with --highres_large; 4 << (--n_sc - 1)
@@ -140,6 +157,28 @@ def _rate(text):
     return p, q
 
 
+def _int_range(flag, lo, hi):
+    """an integer option in lo..hi"""
+    def parse(text):
+        import re
+        if not re.fullmatch(r"[0-9]+", text) or not lo <= int(text) <= hi:
+            raise argparse.ArgumentTypeError(f"{flag} {text}: must be an integer in {lo}..{hi}")
+        return int(text)
+    return parse
+
+
+def _edges(text):
+    """--synth_motion_edges: ascending positive numbers separated by commas -> a tuple of floats"""
+    import math
+    try:
+        v = tuple(float(x) for x in text.split(","))
+    except ValueError:
+        v = ()
+    if not v or any(not math.isfinite(e) or e <= 0 for e in v) or any(a >= b for a, b in zip(v, v[1:])):
+        raise argparse.ArgumentTypeError(f"--synth_motion_edges {text}: expected ascending positive numbers (2,8,32)")
+    return v
+
+
 def _unit_range(flag, hi):
     """a float option in 0..hi"""
     def parse(text):
@@ -202,6 +241,10 @@ GLOBAL = [
     ("--synth_eval", "synth_eval", bool, False, None),
     ("--synth_vgg", "synth_vgg", bool, False, None),
     ("--synth_msssim", "synth_msssim", int, 0, None),
+    ("--synth_motion", "synth_motion", bool, False, None),
+    ("--synth_motion_radius", "synth_motion_radius", _int_range("--synth_motion_radius", 1, 32), 16, None),
+    ("--synth_motion_scale", "synth_motion_scale", _int_range("--synth_motion_scale", 0, 3), 0, None),
+    ("--synth_motion_edges", "synth_motion_edges", _edges, (2.0, 8.0, 32.0), None),
     ("--synth_pad", "synth_pad", str, "none", ["none", "replicate"]),
     ("--synth_window", "synth_window", _window, 0, None),
     ("--synth_yuv", "synth_yuv", str, "bt601", ["bt601", "bt709"]),

@@ -178,16 +178,18 @@ class ExtraTrainer(InterTrainer):
                              "motion that is not there")
         return out
 
-    def _score(self, syn, frames, labels, clip, perceptual=None, msssim=None):
+    def _score(self, syn, frames, labels, clip, perceptual=None, msssim=None, motion=None):
         """--split test --synth_eval, extrapolation: the clip's first two frames are the inputs,
         the next min(--num_pred_step, T - 2) the truth (None: the clip has no third frame);
-        perceptual: the PerceptualScorer of --synth_vgg; msssim: the scales of --synth_msssim"""
+        perceptual: the PerceptualScorer of --synth_vgg; msssim: the scales of --synth_msssim; motion:
+        the MotionSearch of --synth_motion"""
         T = frames.shape[1]
         if T < 3:
             self.log.info(f"synth_eval: skip {clip}: {T} frames, 3 needed")
             return None
         n = 2 + min(getattr(self.args, "num_pred_step", 1), T - 2)
-        return syn.score_extrapolation(frames[:, :n], labels[:, :n], perceptual=perceptual, msssim=msssim)
+        return syn.score_extrapolation(frames[:, :n], labels[:, :n], perceptual=perceptual, msssim=msssim,
+                                       motion=motion)
 
     def save_checkpoint(self):
         return super().save_checkpoint()

@@ -677,10 +677,19 @@ class InterTrainer:
         finally:
             sink.close()
 
-    def _score(self, syn, frames, labels, clip, perceptual=None, msssim=None):
+    def _motion(self):
+        """the synth.MotionSearch of --synth_motion (--synth_motion_radius, --synth_motion_scale), or None"""
+        from ..synth import MotionSearch
+        a = self.args
+        if not getattr(a, "synth_motion", False):
+            return None
+        return MotionSearch(radius=getattr(a, "synth_motion_radius", 16), scale=getattr(a, "synth_motion_scale", 0))
+
+    def _score(self, syn, frames, labels, clip, perceptual=None, msssim=None, motion=None):
         """--split test --synth_eval, interpolation: every 2**synth_levels-th frame is kept, the
         others are synthesised and scored (None: the clip is too short); perceptual: the
-        PerceptualScorer of --synth_vgg; msssim: the scales of --synth_msssim"""
+        PerceptualScorer of --synth_vgg; msssim: the scales of --synth_msssim; motion: the
+        MotionSearch of --synth_motion"""
         step = 1 << getattr(self.args, "synth_levels", 1)
         T = frames.shape[1]
         keep = (T - 1) // step * step + 1
@@ -690,7 +699,7 @@ class InterTrainer:
         if keep < T:
             self.log.info(f"synth_eval: {clip}: the last {T - keep} of {T} frames dropped ((T - 1) % {step} != 0)")
         return syn.score_interpolation(frames[:, :keep], labels[:, :keep], levels=getattr(self.args, "synth_levels", 1),
-                                       perceptual=perceptual, msssim=msssim)
+                                       perceptual=perceptual, msssim=msssim, motion=motion)
 
     def test_eval(self):
         """--split test --synth_eval: the clips of test(), scored instead of written.  Per clip
@@ -706,10 +715,17 @@ class InterTrainer:
         "msssim" per clip, in the summary and in every per_position row, and a top-level
         "msssim_scales"; a clip too small for K scales ends the run with a ValueError naming the
         clip (K is never reduced: one scores.json holds one metric).  With --synth_ensemble other than
-        `none` the synthesis is the ensemble's and a top-level "ensemble" names it."""
+        `none` the synthesis is the ensemble's and a top-level "ensemble" names it.  With
+        --synth_motion every scored slot also gets the synth.MotionScores columns: "motion",
+        "motion_saturated", "tres" and "tres_gt" per clip; "motion", "saturated", "tres", "tres_gt"
+        and "tres_excess" in the summary and in every per_position row; "per_motion", the same
+        columns per bucket of "motion" at --synth_motion_edges; and a top-level "motion" with the
+        block size, the search and the edges.  A clip whose mean saturation exceeds one half is
+        logged once (a reporting rule, not a tuned threshold).  Without the flag the file is what
+        it was."""
         import numpy as np
         from PIL import Image
-        from ..synth import PerceptualScorer, msssim_check, summarize, vgg_region
+        from ..synth import MOTION_BLOCK, MotionScores, PerceptualScorer, motion_grid, msssim_check, summarize, vgg_region
         a = self.args
         if getattr(a, "synth_scd", False):
             self.log.info("synth_eval: --synth_scd is ignored: every held-out frame is scored against its original")
@@ -719,8 +735,10 @@ class InterTrainer:
         syn = self._synthesizer()
         scorer = PerceptualScorer(max_batch=max(1, a.batch_size)) if getattr(a, "synth_vgg", False) else None
         scales = getattr(a, "synth_msssim", 0) or None
+        search = self._motion()
         extra = (("vgg",) if scorer else ()) + (("msssim",) if scales else ())
-        keys = ("psnr", "ssim", "acc", "miou") + extra
+        moving = MotionScores.FIELDS if search else ()  # (the columns of summarize)
+        keys = ("psnr", "ssim", "acc", "miou") + extra + tuple("motion_saturated" if k == "saturated" else k for k in moving)
         img_dir, seg_dir = os.path.join(a.cycgen_load_dir, "rgb"), os.path.join(a.cycgen_load_dir, "seg")
         clips, cols = {}, [[] for _ in range(1 + len(keys))]
         for clip in sorted(d for d in os.listdir(img_dir) if os.path.isdir(os.path.join(img_dir, d))):
@@ -738,25 +756,39 @@ class InterTrainer:
                     msssim_check(*imgs.shape[1:3], scales)
                 except ValueError as e:
                     raise ValueError(f"{clip}: {e}") from None
+            if search:
+                try:
+                    motion_grid(*imgs.shape[1:3], search.scale)
+                except ValueError as e:
+                    raise ValueError(f"{clip}: {e}") from None
             sc = self._on_clip(self._score, syn, torch.from_numpy(imgs)[None].to(self.device),
-                               torch.from_numpy(labs)[None].to(self.device), clip, scorer, scales)
+                               torch.from_numpy(labs)[None].to(self.device), clip, scorer, scales, search)
             if sc is None:
                 continue
-            # psnr, ssim, acc, miou (, vgg) (, msssim) of the one clip
-            vals = [v[0] for v in sc.host(vgg=scorer is not None, msssim=scales is not None)]
+            # psnr, ssim, acc, miou (, vgg) (, msssim) (, motion, saturated, tres, tres_gt) of the one clip
+            vals = [v[0] for v in sc.host(vgg=scorer is not None, msssim=scales is not None, motion=search is not None)]
+            if search and float(np.mean(vals[keys.index("motion_saturated")])) > 0.5:
+                self.log.info("synth_eval: {}: {:.0%} of the blocks have their vector on the border of the search: "
+                              "\"motion\" is a lower bound there; a larger --synth_motion_scale widens the search".format(
+                                  clip, float(np.mean(vals[keys.index("motion_saturated")]))))
             clips[clip] = dict(slots=sc.slots, **{k: v.tolist() for k, v in zip(keys, vals)})
             for col, v in zip(cols, [np.asarray(sc.positions)] + vals):
                 col.append(v)
         for fname in self._y4m_clips(img_dir):
             self.log.info(f"synth_eval: skip {fname}: .y4m clips are synthesised, not scored")
         cat = [np.concatenate(c) for c in cols] if clips else None
-        res = dict(clips=clips, summary=summarize(*cat[:5], **dict(zip(extra, cat[5:]))) if clips else None)
+        edges = tuple(getattr(a, "synth_motion_edges", (2.0, 8.0, 32.0)))
+        more = dict(edges=edges) if search else {}
+        res = dict(clips=clips, summary=summarize(*cat[:5], **dict(zip(extra + moving, cat[5:])), **more) if clips else None)
         if scorer:
             res["vgg_weights"] = scorer.weights_name
         if scales:
             res["msssim_scales"] = scales
         if syn.ensemble is not None:
             res["ensemble"] = syn.ensemble
+        if search:
+            res["motion"] = dict(block=MOTION_BLOCK, radius=search.radius, scale=search.scale, penalty=search.penalty,
+                                 edges=list(edges))
         root = os.path.join(a.cycgen_load_dir, "synth_eval")
         os.makedirs(root, exist_ok=True)
         with open(os.path.join(root, "scores.json"), "w") as f:

@@ -54,6 +54,9 @@ Scoring: `frame_scores` (PSNR, SSIM, label agreement: dvie_synth_score) and, opt
 buffer of my_vgg's forward-only, arena-allocated scoring plan from the uint8 frames, and the
 plan's own cosfeat ops reduce the five feature maps to one float64 per frame; and
 `frame_msssim`, the per-frame multi-scale SSIM over an exact integer pyramid (dvie_synth_msssim).
+Motion (opt-in, `MotionSearch`): `block_motion`, full-search block matching on luma between pairs of
+frames in exact integers (dvie_synth_motion), gives the held-out scores their motion axis and a
+temporal residual across every scored slot (`MotionScores`).
 
 Scene cuts (opt-in, `SceneCuts`): `scene_stats` reduces every neighbouring pair of input frames to
 two integers (luma SAD, 32-bin luma histogram distance: dvie_synth_scene), `scene_cuts` compares
@@ -821,6 +824,125 @@ class SceneCuts:
         return f"SceneCuts(mad={self.mad}, hist={self.hist})"
 
 
+MOTION_BLOCK = 16  # samples of a block side of dvie_synth_motion
+MOTION_MAX_RADIUS, MOTION_MAX_SCALE, MOTION_MAX_PENALTY = 32, 3, 1024
+
+
+class MotionSearch:
+    """The parameters of the block matching (block_motion, score_*(..., motion=)): every 16 x 16
+    block of the luma plane at `scale` (the frame's luma averaged over 2**scale x 2**scale pixels)
+    is searched over (dy, dx) in [-radius, radius]^2 of the reference plane, and a candidate costs
+    its SAD + penalty * (|dy| + |dx|).  radius in 1..32 (plane samples: radius * 2**scale frame
+    pixels), scale in 0..3, penalty in 0..1024, all integers.  The defaults (16, 0, 16) are
+    provisional: they have not been validated on real footage."""
+
+    def __init__(self, radius=16, scale=0, penalty=16):
+        for name, v, lo, hi in (("radius", radius, 1, MOTION_MAX_RADIUS), ("scale", scale, 0, MOTION_MAX_SCALE),
+                                ("penalty", penalty, 0, MOTION_MAX_PENALTY)):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"MotionSearch: {name}={v!r} must be an integer in {lo}..{hi}")
+        self.radius, self.scale, self.penalty = radius, scale, penalty
+
+    def __repr__(self):
+        return f"MotionSearch(radius={self.radius}, scale={self.scale}, penalty={self.penalty})"
+
+
+def motion_grid(H, W, scale):
+    """(bh, bw): the 16 x 16 blocks of the (H >> scale, W >> scale) plane of an (H, W) frame, edge
+    blocks included (ValueError when the frame has no sample at that scale)"""
+    if not 0 <= scale <= MOTION_MAX_SCALE:
+        raise ValueError(f"motion_grid: scale={scale} must be in 0..{MOTION_MAX_SCALE}")
+    if H < (1 << scale) or W < (1 << scale):
+        raise ValueError(f"motion_grid: a {H}x{W} frame has no sample at scale={scale}")
+    return -(-(H >> scale) // MOTION_BLOCK), -(-(W >> scale) // MOTION_BLOCK)
+
+
+class MotionStats:
+    """What block_motion returns: the int64 device tensors `d2`, `sad`, `sad0`, `border`, shaped like
+    the leading dimensions of the frames (per pair the sums over its blocks of the winning
+    vector's squared length in plane samples, of the winners' SAD, of the SAD at (0, 0), and the
+    number of blocks whose winner lies on the border of the search); `blocks` per pair, `samples`
+    = blocks * 256 and `scale`; with vectors=True also `mv`, int16 (..., bh, bw, 2) holding
+    (dy, dx), and `bsad`, the winner's and the zero SAD (..., bh, bw, 2) (the device's uint32 in
+    an int32 tensor: a block SAD is at most 65 280); None otherwise.  rms, residual, residual0
+    and saturated are derived on the device in float64."""
+
+    def __init__(self, d2, sad, sad0, border, blocks, scale, mv=None, bsad=None):
+        self.d2, self.sad, self.sad0, self.border = d2, sad, sad0, border
+        self.blocks, self.samples, self.scale = blocks, blocks * MOTION_BLOCK * MOTION_BLOCK, scale
+        self.mv, self.bsad = mv, bsad
+
+    def _over(self, t, n):  # (a tensor divisor: torch turns a division by a Python scalar into a multiplication)
+        return t.double() / torch.full_like(t, n, dtype=torch.float64)
+
+    @property
+    def rms(self):
+        """sqrt(d2 / blocks) * 2**scale: the RMS block displacement in frame pixels"""
+        return torch.sqrt(self._over(self.d2, self.blocks)) * float(1 << self.scale)
+
+    @property
+    def residual(self):
+        """sad / samples: the mean absolute difference after motion compensation, in grey levels"""
+        return self._over(self.sad, self.samples)
+
+    @property
+    def residual0(self):
+        """sad0 / samples: the same without motion compensation"""
+        return self._over(self.sad0, self.samples)
+
+    @property
+    def saturated(self):
+        """border / blocks: the fraction of blocks for which the search may have been too small"""
+        return self._over(self.border, self.blocks)
+
+
+def block_motion(cur, ref, search=None, vectors=False):
+    """Block-matching motion statistics of uint8 device frames `cur` (..., H, W, 3) against `ref`
+    (the frames frame_scores takes: up to two leading dimensions of any strides -- x[:, 1:] against
+    x[:, :-1] of one clip runs in place -- the frame-level dimensions contiguous) -> MotionStats
+    shaped like the leading dimensions.  search: a MotionSearch (None: the defaults).
+    dvie_synth_motion: the luma planes, the matcher and a finalize launch; exact integers, no host
+    synchronisation; include/dvie.h has the definition."""
+    search = MotionSearch() if search is None else search
+    if not isinstance(search, MotionSearch):
+        raise ValueError(f"search: a MotionSearch, got {search!r}")
+    lead, H, W, n0, n1, strides = _pairs_of(cur, ref)
+    bh, bw = motion_grid(H, W, search.scale)
+    d = L.SynthMotionDesc()
+    d.cur, d.ref, d.n0, d.n1, d.h, d.w = cur.data_ptr(), ref.data_ptr(), n0, n1, H, W
+    d.cur_s0, d.cur_s1, d.ref_s0, d.ref_s1 = strides
+    d.radius, d.scale, d.penalty = search.radius, search.scale, search.penalty
+    dev = cur.device
+    sums = [torch.empty(lead, dtype=torch.int64, device=dev) for _ in range(4)]
+    d.d2, d.sad, d.sad0, d.border = (t.data_ptr() for t in sums)
+    mv = bsad = None
+    if vectors:
+        mv = torch.empty(lead + (bh, bw, 2), dtype=torch.int16, device=dev)
+        bsad = torch.empty(lead + (bh, bw, 2), dtype=torch.int32, device=dev)
+        d.mv, d.bsad = mv.data_ptr(), bsad.data_ptr()
+    lib = L.load()
+    ws = torch.empty((lib.dvie_synth_motion_ws_bytes(ctypes.byref(d)),), dtype=torch.uint8, device=dev)
+    d.ws = ws.data_ptr()
+    L.check(lib.dvie_synth_motion(ctypes.byref(d), L.stream_ptr(dev)), "synth motion")
+    return MotionStats(*sums, bh * bw, search.scale, mv, bsad)
+
+
+class MotionScores:
+    """The motion columns of score_interpolation / score_extrapolation(..., motion=): four float64
+    device tensors (B, len(slots)).  `motion`: MotionStats.rms of the later against the earlier of
+    the two original input frames that bracket the slot (extrapolation: of the second against the
+    first input frame, the same value at every step), in pixels per input interval; `saturated`:
+    the same pairs' MotionStats.saturated; `tres`: the motion-compensated residual of the
+    synthesised video across the slot (interpolation: the mean of the residuals of output frame t
+    against output frames t - 1 and t + 1; extrapolation: of prediction k against prediction k - 1,
+    for k = 0 against the second input frame); `tres_gt`: the same on the originals.  tres -
+    tres_gt is the flicker the synthesis added."""
+    FIELDS = ("motion", "saturated", "tres", "tres_gt")
+
+    def __init__(self, motion, saturated, tres, tres_gt):
+        self.motion, self.saturated, self.tres, self.tres_gt = motion, saturated, tres, tres_gt
+
+
 RETIME_MAX = 4096  # the largest P and Q of a Retime (dvie_synth_retime's den)
 RETIME_MODES = ("nearest", "blend")
 
@@ -1082,13 +1204,30 @@ def frame_scores(pred, gt, pred_labels=None, gt_labels=None, n_classes=20, perce
     return out
 
 
-def summarize(position, psnr, ssim, acc, miou, vgg=None, msssim=None):
+def motion_bucket_names(edges):
+    """the keys of summarize's per_motion rows for the ascending positive `edges`: "0-e0", "e0-e1",
+    ..., "e_last-inf" (ValueError for edges that are not ascending positive numbers)"""
+    import math
+    edges = [float(e) for e in edges]
+    if not edges or any(not math.isfinite(e) or e <= 0 for e in edges) or any(a >= b for a, b in zip(edges, edges[1:])):
+        raise ValueError(f"edges={edges} must be ascending positive numbers")
+    names = ["0"] + [f"{e:g}" for e in edges] + ["inf"]
+    return [f"{a}-{b}" for a, b in zip(names, names[1:])]
+
+
+def summarize(position, psnr, ssim, acc, miou, vgg=None, msssim=None, motion=None, saturated=None, tres=None,
+              tres_gt=None, edges=None):
     """Host-side means of per-frame scores (numpy arrays of one length; `position` an integer
     per frame) -> {"psnr", "ssim", "acc", "miou", "frames", "per_position": {position: the same
     four and "frames"}} as Python floats.  The mean PSNR is the mean of the per-frame PSNRs
     (losses.py:103-116); an infinite value stays infinite.  With `vgg` (the per-frame perceptual
     scores) the result and every per_position row also have "vgg", with `msssim` (the per-frame
-    multi-scale SSIM) "msssim"."""
+    multi-scale SSIM) "msssim".  With the per-frame MotionScores columns `motion`, `saturated`,
+    `tres` and `tres_gt` they also have those means, and with both `tres` and `tres_gt`
+    "tres_excess" = mean(tres - tres_gt), the flicker the synthesis added.  With `edges` (ascending
+    positive floats; needs `motion`) the result also has "per_motion": one row with the columns of
+    a per_position row per bucket [0, e0), [e0, e1), ..., [e_last, inf) of the per-frame `motion`,
+    keyed by motion_bucket_names ("2-8"); empty buckets are omitted."""
     import numpy as np
     position = np.asarray(position)
     cols = dict(psnr=np.asarray(psnr, dtype=np.float64), ssim=np.asarray(ssim, dtype=np.float64),
@@ -1097,6 +1236,13 @@ def summarize(position, psnr, ssim, acc, miou, vgg=None, msssim=None):
         cols["vgg"] = np.asarray(vgg, dtype=np.float64)
     if msssim is not None:
         cols["msssim"] = np.asarray(msssim, dtype=np.float64)
+    for k, v in (("motion", motion), ("saturated", saturated), ("tres", tres), ("tres_gt", tres_gt)):
+        if v is not None:
+            cols[k] = np.asarray(v, dtype=np.float64)
+    if tres is not None and tres_gt is not None:
+        cols["tres_excess"] = cols["tres"] - cols["tres_gt"]
+    if edges is not None and motion is None:
+        raise ValueError("summarize: edges needs the per-frame motion")
 
     def means(sel):
         with np.errstate(invalid="ignore"):
@@ -1106,6 +1252,10 @@ def summarize(position, psnr, ssim, acc, miou, vgg=None, msssim=None):
 
     out = means(np.ones(position.shape, dtype=bool))
     out["per_position"] = {int(p): means(position == p) for p in sorted(set(position.tolist()))}
+    if edges is not None:
+        names = motion_bucket_names(edges)
+        bucket = np.searchsorted(np.asarray(edges, dtype=np.float64), cols["motion"], side="right")  # e belongs to [e, next)
+        out["per_motion"] = {names[b]: means(bucket == b) for b in range(len(names)) if np.any(bucket == b)}
     return out
 
 
@@ -1116,38 +1266,45 @@ class SynthScores:
     values are also attributes here (sse, ssim, agree, valid, inter, uni, psnr, acc, miou, vgg
     when a PerceptualScorer was passed and msssim when a number of scales was);
     `frames` / `labels`, the synthesised video as interpolate / extrapolate returns it;
-    `positions`, per slot the position the summary groups by (slot % 2**levels, or the step)."""
+    `positions`, per slot the position the summary groups by (slot % 2**levels, or the step);
+    `motion`, the MotionScores when a MotionSearch was passed, None otherwise."""
 
-    def __init__(self, slots, positions, scores, frames, labels):
+    def __init__(self, slots, positions, scores, frames, labels, motion=None):
         self.slots, self.positions, self.scores, self.frames, self.labels = list(slots), list(positions), scores, frames, labels
+        self.motion = motion
 
     def __getattr__(self, name):
         if name in FrameScores.FIELDS or name in ("psnr", "acc", "miou"):
             return getattr(self.scores, name)
         raise AttributeError(name)
 
-    def host(self, vgg=False, msssim=False):
+    def host(self, vgg=False, msssim=False, motion=False):
         """psnr, ssim, acc, miou -- with vgg=True also vgg (scored with a PerceptualScorer), with
-        msssim=True also msssim (scored with msssim=K), after the others -- as float64 numpy
+        msssim=True also msssim (scored with msssim=K), with motion=True also motion, saturated,
+        tres and tres_gt (scored with motion=), each after the others -- as float64 numpy
         arrays (B, len(slots)): one copy to the host"""
         s = self.scores
+        if motion and self.motion is None:
+            raise ValueError("these scores have no motion columns (score_* was called without motion=)")
         if vgg and s.vgg is None:
             raise ValueError("these scores have no vgg column (score_* was called without perceptual=)")
         if msssim and s.msssim is None:
             raise ValueError("these scores have no msssim column (score_* was called without msssim=)")
         return tuple(torch.stack([s.psnr, s.ssim, s.acc, s.miou] + ([s.vgg] if vgg else [])
-                                 + ([s.msssim] if msssim else [])).cpu().numpy())
+                                 + ([s.msssim] if msssim else [])
+                                 + ([getattr(self.motion, k) for k in MotionScores.FIELDS] if motion else [])).cpu().numpy())
 
     def summary(self):
         """Means over all scored frames and per position (summarize) as Python floats -- the
-        one place that copies to the host.  "vgg" and "msssim" are included when the scores have
-        them."""
+        one place that copies to the host.  "vgg", "msssim" and the motion columns (with
+        "tres_excess") are included when the scores have them."""
         import numpy as np
         extra = [k for k in ("vgg", "msssim") if getattr(self.scores, k) is not None]
-        cols = self.host(**{k: True for k in extra})
+        cols = self.host(**{k: True for k in extra}, motion=self.motion is not None)
+        names = extra + (list(MotionScores.FIELDS) if self.motion is not None else [])
         pos = np.broadcast_to(np.asarray(self.positions), cols[0].shape)
         return summarize(pos.ravel(), *[c.ravel() for c in cols[:4]],
-                         **{k: c.ravel() for k, c in zip(extra, cols[4:])})
+                         **{k: c.ravel() for k, c in zip(names, cols[4:])})
 
 
 class FrameSizeError(ValueError):
@@ -1734,7 +1891,7 @@ class VideoSynthesizer:
         return fr[2:].transpose(0, 1), lb[2:].transpose(0, 1)
 
     # ---------------- held-out scoring ----------------
-    def score_interpolation(self, frames, labels, levels=1, perceptual=None, msssim=None):
+    def score_interpolation(self, frames, labels, levels=1, perceptual=None, msssim=None, motion=None):
         """Held-out scoring of interpolation: frames (B, T, H, W, 3) and labels (B, T, H, W) of
         real clips with (T - 1) % 2**levels == 0 and T > 2**levels.  Frames 0, 2**levels, ...
         go through interpolate(..., levels); every other slot t is scored against original
@@ -1742,8 +1899,12 @@ class VideoSynthesizer:
         slots at one offset inside the period are one strided (B, G) view of the synthesised
         and of the original video, scored in place: 2**levels - 1 scoring calls.
         perceptual: a PerceptualScorer -> the scores also have `.vgg` (frame_scores); msssim: a
-        number of scales K -> they also have `.msssim`."""
+        number of scales K -> they also have `.msssim`; motion: a MotionSearch -> the result
+        also has `.motion`, the MotionScores of the slots (block_motion: the bracketing inputs'
+        motion and the temporal residual across every slot, 4 * (2**levels - 1) + 1 calls)."""
         self._check(frames, labels)
+        if motion is not None and not isinstance(motion, MotionSearch):
+            raise ValueError(f"motion: a MotionSearch, got {motion!r}")
         if perceptual is not None:
             vgg_region(*frames.shape[2:4])  # (too small a frame fails before the synthesis runs)
         if msssim is not None:
@@ -1761,15 +1922,33 @@ class VideoSynthesizer:
                 continue
             t = torch.stack([getattr(p, k) for p in parts], dim=2)
             setattr(scores, k, t.reshape((t.shape[0], len(slots)) + tuple(t.shape[3:])))
-        return SynthScores(slots, [t % step for t in slots], scores, out_f, out_l)
+        ms = None
+        if motion is not None:
+            G = (T - 1) // step
+            br = block_motion(frames[:, step::step], frames[:, :-step:step], motion)  # (B, G): later against earlier
 
-    def score_extrapolation(self, frames, labels, perceptual=None, msssim=None):
+            def per_slot(t):  # (B, G) per pair -> (B, G * (step - 1)): the pair's value at each of its slots
+                return t.unsqueeze(2).expand(-1, -1, step - 1).reshape(t.shape[0], len(slots))
+
+            def tres_of(video):  # slot t = g * step + o: the residuals against slots t - 1 and t + 1, averaged
+                parts = [(block_motion(video[:, o::step], video[:, o - 1::step][:, :G], motion).residual
+                          + block_motion(video[:, o::step], video[:, o + 1::step][:, :G], motion).residual) * 0.5
+                         for o in range(1, step)]
+                return torch.stack(parts, dim=2).reshape(-1, len(slots))
+
+            ms = MotionScores(per_slot(br.rms), per_slot(br.saturated), tres_of(out_f), tres_of(frames))
+        return SynthScores(slots, [t % step for t in slots], scores, out_f, out_l, ms)
+
+    def score_extrapolation(self, frames, labels, perceptual=None, msssim=None, motion=None):
         """Held-out scoring of extrapolation: frames (B, 2 + S, H, W, 3), S >= 1.  The first two
         frames are the inputs of extrapolate(..., steps=S); step k is scored against original
         frame 2 + k -> SynthScores with slots 0 .. S-1, tensors (B, S).
         perceptual: a PerceptualScorer -> the scores also have `.vgg` (frame_scores); msssim: a
-        number of scales K -> they also have `.msssim`."""
+        number of scales K -> they also have `.msssim`; motion: a MotionSearch -> the result
+        also has `.motion`, the MotionScores of the steps (block_motion, three calls)."""
         self._check(frames, labels)
+        if motion is not None and not isinstance(motion, MotionSearch):
+            raise ValueError(f"motion: a MotionSearch, got {motion!r}")
         if perceptual is not None:
             vgg_region(*frames.shape[2:4])
         if msssim is not None:
@@ -1780,4 +1959,11 @@ class VideoSynthesizer:
         out_f, out_l = self.extrapolate(frames[:, :2], labels[:, :2], steps=S)
         scores = frame_scores(out_f, frames[:, 2:], out_l, labels[:, 2:], n_classes=self.cm.n_classes,
                               perceptual=perceptual, msssim=msssim)
-        return SynthScores(range(S), range(S), scores, out_f, out_l)
+        ms = None
+        if motion is not None:
+            br = block_motion(frames[:, 1:2], frames[:, 0:1], motion)  # (B, 1): the second input against the first
+            video = torch.cat([frames[:, 1:2], out_f], dim=1)  # the second input, then the predictions
+            ms = MotionScores(br.rms.expand(-1, S), br.saturated.expand(-1, S),
+                              block_motion(video[:, 1:], video[:, :-1], motion).residual,
+                              block_motion(frames[:, 2:], frames[:, 1:-1], motion).residual)
+        return SynthScores(range(S), range(S), scores, out_f, out_l, ms)

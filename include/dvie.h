@@ -1356,6 +1356,70 @@ typedef struct dvie_synth_ens_acc_desc {
 
 int dvie_synth_ens_acc(const dvie_synth_ens_acc_desc* d, void* stream);
 
+/*
+ * dvie_synth_motion: full-search block matching on luma between pairs of uint8 frames
+ * (synth.block_motion; DESIGN.md "Motion statistics").  Integer arithmetic only, so that every
+ * implementation agrees to the last bit.
+ *
+ * Frames: n0 * n1 pairs; frame (i0, i1) of `cur` at cur + i0*cur_s0 + i1*cur_s1 BYTES and of `ref`
+ * at ref + i0*ref_s0 + i1*ref_s1 BYTES (strides may be anything: the views x[:, 1:] and x[:, :-1]
+ * of one tensor, a transposed view of slot-major storage); a frame is a contiguous h*w*3 block of
+ * uint8 RGB.  No alignment of frame bases is assumed.
+ *   Y        = (77*R + 150*G + 29*B + 128) >> 8 per pixel (dvie_synth_scene's luma)
+ *   plane P  of size (hs, ws) = (h >> s, w >> s) at scale s:  s = 0: P = Y;  s >= 1:
+ *              P[y][x] = (sum of Y over the 2^s x 2^s block at (y << s, x << s) + 2^(2s-1)) >> 2s;
+ *              trailing rows and columns that fill no block are dropped (dvie_synth_msssim's rule)
+ *   P~[y][x] = P[clamp(y, 0, hs-1)][clamp(x, 0, ws-1)] for any integers y, x
+ *   blocks     bh = ceil(hs / 16), bw = ceil(ws / 16); block (i, j) is ALWAYS the 16 x 16 samples
+ *              C~[16i+u][16j+v], u, v < 16, of the cur plane: edge blocks read the extension,
+ *              nothing is masked
+ *   candidates (dy, dx) in [-R, R]^2 with the ref plane R~:
+ *              SAD  = sum over u, v < 16 of |C~[16i+u][16j+v] - R~[16i+u+dy][16j+v+dx]|
+ *              cost = SAD + penalty * (|dy| + |dx|)
+ *   winner     the candidate with the lexicographically smallest (cost, dy*dy + dx*dx, dy, dx);
+ *              no other tie rule (two flat frames give zero vectors everywhere)
+ * Outputs, indexed f = i0*n1 + i1, all written by the call (nothing is accumulated into, two
+ * calls give the same bits), int64:
+ *   d2[f]      sum over the blocks of the winner's dy*dy + dx*dx, in plane units
+ *   sad[f]     sum of the winners' SAD
+ *   sad0[f]    sum of the SAD at (0, 0)
+ *   border[f]  blocks whose winner has max(|dy|, |dx|) == R (the search may have been too small)
+ * Optional per-block outputs, both or neither (NULL):
+ *   mv         int16  [f][bh][bw][2]: (dy, dx)
+ *   bsad       uint32 [f][bh][bw][2]: the winner's SAD, the SAD at (0, 0)
+ * Widths: a block SAD is <= 256 * 255 = 65 280; a cost is <= 65 280 + 1024 * 64 < 2^18; d2 of a
+ * block is <= 2 * 32^2 = 2048; the per-block values are uint32 and the per-pair sums int64.
+ * Limits: radius R in 1..32, scale s in 0..3, penalty in 0..1024, 2^s <= h, w <= 65536,
+ * n0 * n1 <= 65535; anything else is DVIE_EINVAL with a message that names the value, before any
+ * launch.
+ * Launches: two that write the cur and ref luma planes at scale s with their clamped margins into
+ * the workspace, the matcher (a workgroup stages the search window of four neighbouring blocks in
+ * LDS, a wave owns a block, its lanes share the candidates, v_sad_u8 forms the SADs and a wave
+ * minimum over one packed key per lane picks the winner), a finalize launch that sums the block
+ * values per pair.  No atomics on global memory, no host synchronisation.
+ * ws: dvie_synth_motion_ws_bytes(d) bytes (0 for a descriptor whose sizes are invalid), 16-byte
+ * aligned, fully overwritten: with groups = ceil(bw / 4), the cur planes (n0*n1 x 16 bh x
+ * 64 groups bytes), the ref planes (n0*n1 x (16 bh + 2R) x (64 groups + 2R rounded up to 4, + 4)
+ * bytes), each rounded up to 16, and 16 bytes per block.  d2, sad, sad0, border 8-byte aligned.
+ */
+typedef struct dvie_synth_motion_desc {
+  const uint8_t* cur;
+  const uint8_t* ref;
+  long long* d2;
+  long long* sad;
+  long long* sad0;
+  long long* border;
+  int16_t* mv;
+  uint32_t* bsad;
+  void* ws;
+  long long cur_s0, cur_s1, ref_s0, ref_s1; /* byte strides of (i0, i1) */
+  int n0, n1, h, w;
+  int radius, scale, penalty, pad0;
+} dvie_synth_motion_desc;
+
+size_t dvie_synth_motion_ws_bytes(const dvie_synth_motion_desc* d);
+int dvie_synth_motion(const dvie_synth_motion_desc* d, void* stream);
+
 int dvie_run_ops(const dvie_op* ops, int n, void* stream);
 
 /* The pairs of ops dvie_run_ops(ops, n) runs as chained launches (host only, nothing is
@@ -1373,7 +1437,7 @@ int dvie_ops_chain_pairs(const dvie_op* ops, int n, int* partner);
  * descriptors outside the op list: warp, softmax, sn_layer, clip, synth_load, synth_finish,
  * synth_bridge, synth_score, synth_load_pad, synth_finish_crop, synth_vgg_load, synth_msssim, synth_yuv,
  * synth_scene, synth_cutfill, synth_tile_blend; 116 is unused and answers 0; 117: synth_retime,
- * 118: synth_flip, 119: synth_ens_acc). */
+ * 118: synth_flip, 119: synth_ens_acc; 120 is unused and answers 0; 121: synth_motion). */
 size_t dvie_abi_sizeof(int which);
 /* library version string */
 const char* dvie_version(void);

@@ -552,6 +552,36 @@ def scene_numbers(dev, seconds):
     return out
 
 
+def motion_numbers(dev, seconds):
+    """block_motion on one 1080p pair at (R, s) = (16, 0), (16, 1), (32, 0), alternating, three rounds;
+    buffer sets past the Infinity Cache.  bytes: the frames' own (2 x 3 H W); SAD operations: blocks x
+    (2R+1)^2 candidates x 256 absolute differences"""
+    from deep_video_interpolation_extrapolation_amd.synth import MotionSearch, block_motion, motion_grid
+    H, W = 1080, 1920
+    pair_bytes = 2 * H * W * 3
+    sets = (320 << 20) // pair_bytes + 1
+    pairs = [torch.randint(0, 256, (2, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(sets)]
+    k = [0]
+
+    def rot(search):
+        def run():
+            i = k[0] = (k[0] + 1) % sets
+            block_motion(pairs[i][1], pairs[i][0], search)
+        return run
+
+    configs = {f"R{r}_s{s}": MotionSearch(r, s, 16) for r, s in ((16, 0), (16, 1), (32, 0))}
+    rates = _alternate({name: rot(search) for name, search in configs.items()}, seconds)
+    out = dict(buffer_sets=sets, pair_bytes=pair_bytes)
+    for name, v in rates.items():
+        search = configs[name]
+        bh, bw = motion_grid(H, W, search.scale)
+        diffs = bh * bw * (2 * search.radius + 1) ** 2 * 256
+        mid = sorted(v)[1]
+        out[name] = dict(us=1e6 / mid, runs_us=[1e6 / r for r in v], spread=(max(v) - min(v)) / mid, blocks=bh * bw,
+                         abs_diffs=diffs, tera_diffs_per_s=diffs * mid / 1e12, frame_tbs=pair_bytes * mid / 1e12)
+    return out
+
+
 def make_inter_net():
     a = types.SimpleNamespace(syn_type="inter", highres_large=False, coarse_model="HRNet", precision="bf16")
     torch.manual_seed(1024)
@@ -950,7 +980,15 @@ def main():
     ap.add_argument("--scene", action="store_true", help="only the scene-cut legs")
     ap.add_argument("--tile", action="store_true", help="only the tiled-synthesis legs")
     ap.add_argument("--ensemble", action="store_true", help="only the self-ensemble legs")
+    ap.add_argument("--motion", action="store_true", help="only the block-matching legs")
     a = ap.parse_args()
+    if a.motion:
+        res = dict(motion_1x1080x1920=motion_numbers(torch.device("cuda:0"), a.seconds))
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.ensemble:
         res = dict(ensemble_interpolate_bf16=ensemble_numbers(torch.device("cuda:0"), a.seconds))
         print(json.dumps(res, indent=1))
