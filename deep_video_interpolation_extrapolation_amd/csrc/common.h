@@ -173,6 +173,23 @@ __device__ __forceinline__ void acc_rows8(const f32x16& acc, float (*v)[8]) {
 
 __host__ __device__ __forceinline__ int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// The values of a block's N threads summed through a fixed LDS tree, the same bits every run:
+// store, barrier, then halving steps from the power of two at or above N / 2 (the t + k < N guard
+// folds away where N is a power of two).  The sum ends in s[0], which every thread may read.
+constexpr int lds_tree_top(int n) { return n <= 2 ? 1 : 2 * lds_tree_top((n + 1) / 2); }
+template <int N, typename T>
+__device__ __forceinline__ void lds_tree_sum(T v, T* s) {
+  constexpr int top = lds_tree_top(N);
+  const int t = threadIdx.x;
+  s[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int k = top; k > 0; k >>= 1) {
+    if (t < k && t + k < N) s[t] += s[t + k];
+    __syncthreads();
+  }
+}
+
 // One LDS-DMA piece (buffer_load_dwordx4 ... lds: 64 lanes x 16 B into LDS at dst + 16 * lane)
 // issued through inline asm.  With __builtin_amdgcn_raw_ptr_buffer_load_lds the compiler
 // sees an LDS write behind the load and puts s_waitcnt vmcnt(0) before the next LDS read, so

@@ -29,6 +29,7 @@
 //
 // motion_finalize_kernel: one workgroup of 1024 threads per pair sums the block values in int64.
 #include "common.h"
+#include "pixel.h"
 
 namespace dvie {
 
@@ -81,10 +82,6 @@ __host__ __device__ __forceinline__ mo_ws mo_ws_of(void* ws, const mo_geom& g, l
   return r;
 }
 
-__device__ __forceinline__ uint32_t mo_luma(const uint8_t* q) {
-  return (77u * q[0] + 150u * q[1] + 29u * q[2] + 128u) >> 8;
-}
-
 }  // namespace
 
 // which: 0 the cur planes, 1 the ref planes.  grid (rows * chunks, pairs)
@@ -108,11 +105,11 @@ __global__ __launch_bounds__(MO_T) void motion_plane_kernel(const dvie_synth_mot
     const uint8_t* q = src + (((sy << s) * p.w) + (sx << s)) * 3;
     uint32_t v;
     if (s == 0) {
-      v = mo_luma(q);
+      v = px_luma(q);
     } else {
       uint32_t sum = 0;
       for (int a = 0; a < n; ++a)
-        for (int b = 0; b < n; ++b) sum += mo_luma(q + ((long long)a * p.w + b) * 3);
+        for (int b = 0; b < n; ++b) sum += px_luma(q + ((long long)a * p.w + b) * 3);
       v = (sum + (1u << (2 * s - 1))) >> (2 * s);
     }
     out |= v << (8 * k);

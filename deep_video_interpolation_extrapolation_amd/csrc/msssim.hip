@@ -9,21 +9,19 @@
 // exact).  Integer arithmetic only.  A level's pixel (i, j) exists iff its whole block lies in the
 // image ((i + 1) << s <= h), so no written value depends on a sample outside it.
 //
-// msssim_level_kernel: the row walk of synth_score_kernel (score.hip) over the sample type: a
-// workgroup of 192 threads owns a 64-pixel strip of a 32-row segment of ONE LEVEL of one pair,
-// thread t one (pixel, channel) item; per input row the 222-sample span of both images goes as
-// float64 into one of two LDS row buffers, the five horizontal 11-tap sums live in a register
-// ring of 11 rows, one barrier per row.  Samples are the bytes of the frames at level 0 and the
-// uint16 sums of the workspace above it; C1, C2 come per level, scaled by (255 * 4^s)^2.  The
-// grid's x dimension runs over the blocks of all K levels (level 0 first), so the small coarse
-// levels fill the tail of the large one instead of being launches of a few blocks each.  A block
-// sums cs, on the last level l * cs, and leaves one float64 partial through a fixed LDS tree.
+// msssim_level_kernel: the row walk of ssim_walk.h (a workgroup of 192 threads, a 64-pixel strip
+// of a 32-row segment, thread t one (pixel, channel) item) over ONE LEVEL of one pair.  Samples
+// are the bytes of the frames at level 0 and the uint16 sums of the workspace above it; C1, C2
+// come per level, scaled by (255 * 4^s)^2.  The grid's x dimension runs over the blocks of all K
+// levels (level 0 first), so the small coarse levels fill the tail of the large one instead of
+// being launches of a few blocks each.  A block sums cs, on the last level l * cs, and leaves one
+// float64 partial through the fixed LDS tree of common.h.
 //
 // msssim_finalize_kernel: one block of five waves per pair; wave s sums the partials of level s in
 // a fixed order and divides by 3 * h_s * w_s -> parts and its power (float64 pow); thread 0
 // multiplies the K powers in order -> msssim.
 #include "common.h"
-#include "gauss11.h"
+#include "ssim_walk.h"
 
 #include <algorithm>
 
@@ -31,11 +29,6 @@ namespace dvie {
 
 namespace {
 
-constexpr int MS_PX = 64;              // pixels of a strip
-constexpr int MS_IT = 3 * MS_PX;       // items (= threads) of a level-pass block
-constexpr int MS_SEG = 32;             // output rows of a segment
-constexpr int MS_HALO = 15;            // samples of halo on each side (5 pixels)
-constexpr int MS_SPAN = MS_IT + 2 * MS_HALO;
 constexpr int MS_MAXK = 5;
 constexpr int MS_WIN = 11;
 constexpr int PY_ROWS = 16, PY_PX = 64, PY_IT = 3 * PY_PX, PY_THREADS = 256;
@@ -77,9 +70,9 @@ bool ms_plan_of(const dvie_synth_msssim_desc* d, ms_plan* q) {
     l.c2 = (0.03 * scale) * (0.03 * scale);
     l.h = d->h >> s;
     l.w = d->w >> s;
-    l.strips = (l.w + MS_PX - 1) / MS_PX;
+    l.strips = (l.w + SW_PX - 1) / SW_PX;
     l.blk0 = (int)blk;
-    blk += (long long)l.strips * ((l.h + MS_SEG - 1) / MS_SEG);
+    blk += (long long)l.strips * ((l.h + SW_SEG - 1) / SW_SEG);
     l.src = src;
     if (s >= 1) src += ((2LL * q->N * l.h * l.w * 3 + 3) / 4) * 4;  // (levels start 8-byte aligned)
     q->wt[s] = W5[s] / wsum;
@@ -167,9 +160,8 @@ struct ms_row {
 
 }  // namespace
 
-__global__ __launch_bounds__(MS_IT) void msssim_level_kernel(const dvie_synth_msssim_desc p, const ms_plan q) {
-  __shared__ double s_row[2][2][MS_SPAN];
-  __shared__ double s_red[MS_IT];
+__global__ __launch_bounds__(SW_IT) void msssim_level_kernel(const dvie_synth_msssim_desc p, const ms_plan q) {
+  __shared__ double s_red[SW_IT];
 
   const int t = threadIdx.x, f = blockIdx.y;
   const int bid = (int)blockIdx.x;
@@ -180,8 +172,8 @@ __global__ __launch_bounds__(MS_IT) void msssim_level_kernel(const dvie_synth_ms
   const ms_level lv = q.lv[s];
   const int local = bid - lv.blk0;
   const int seg = local / lv.strips, strip = local - seg * lv.strips;
-  const int x0 = strip * MS_PX, y0 = seg * MS_SEG;
-  const int y1 = min(y0 + MS_SEG, lv.h), rend = y1 + 5;
+  const int x0 = strip * SW_PX, y0 = seg * SW_SEG;
+  const int y1 = min(y0 + SW_SEG, lv.h);
   const long long rowb = 3LL * lv.w;
   const bool wide = s > 0;  // uint16 sums of the workspace; level 0: the frames' bytes
   const long long img = (long long)lv.h * rowb;
@@ -189,113 +181,38 @@ __global__ __launch_bounds__(MS_IT) void msssim_level_kernel(const dvie_synth_ms
   const uint16_t* wb = wa + img;
   const uint8_t* pa = ms_frame(p.pred, p.pred_s0, p.pred_s1, f, p.n1);
   const uint8_t* pb = ms_frame(p.gt, p.gt_s0, p.gt_s1, f, p.n1);
-  const bool last = s == q.K - 1;
+  const bool last = s == q.K - 1;  // the luminance factor multiplies in on the last level only
 
-  const long long col = 3LL * x0 + t;  // this thread's sample within the image row
-  const bool colok = col < rowb;
-  // threads 0..29 also fetch one halo sample: span positions 0..14 and 207..221
-  const int hpos = t < MS_HALO ? t : MS_IT + t;
-  const long long hcol = 3LL * x0 - MS_HALO + hpos;
-  const bool hok = t < 2 * MS_HALO && hcol >= 0 && hcol < rowb;
-
+  const ssim_cols c = ssim_cols_of(x0, rowb);
   auto fetch = [&](int r) {
     ms_row v = {0, 0, 0, 0};
     if (r >= 0 && r < lv.h) {
       const long long o = r * rowb;
       if (wide) {
-        if (colok) {
-          v.a = wa[o + col];
-          v.b = wb[o + col];
+        if (c.colok) {
+          v.a = wa[o + c.col];
+          v.b = wb[o + c.col];
         }
-        if (hok) {
-          v.ha = wa[o + hcol];
-          v.hb = wb[o + hcol];
+        if (c.hok) {
+          v.ha = wa[o + c.hcol];
+          v.hb = wb[o + c.hcol];
         }
       } else {
-        if (colok) {
-          v.a = pa[o + col];
-          v.b = pb[o + col];
+        if (c.colok) {
+          v.a = pa[o + c.col];
+          v.b = pb[o + c.col];
         }
-        if (hok) {
-          v.ha = pa[o + hcol];
-          v.hb = pb[o + hcol];
+        if (c.hok) {
+          v.ha = pa[o + c.hcol];
+          v.hb = pb[o + c.hcol];
         }
       }
     }
     return v;
   };
+  const double acc = ssim_walk(c, y0, y1, lv.h, lv.c1, lv.c2, last, fetch, [](int, const ms_row&) {});
 
-  double ring[11][5];
-#pragma unroll
-  for (int k = 0; k < 11; ++k)
-#pragma unroll
-    for (int j = 0; j < 5; ++j) ring[k][j] = 0.0;
-  const double C1 = lv.c1, C2 = lv.c2;
-  double acc = 0.0;
-
-  ms_row cur = fetch(y0 - 5);
-  int it = 0;  // rows consumed: row r = y0 - 5 + it sits in ring slot it % 11
-  for (int base = y0 - 5; base < rend; base += 11) {
-#pragma unroll
-    for (int u = 0; u < 11; ++u) {
-      const int r = base + u;
-      if (r >= rend) continue;  // (uniform over the block; the tail of the last group of 11)
-      const int par = it & 1;
-      s_row[par][0][MS_HALO + t] = (double)cur.a;
-      s_row[par][1][MS_HALO + t] = (double)cur.b;
-      if (t < 2 * MS_HALO) {
-        s_row[par][0][hpos] = (double)cur.ha;
-        s_row[par][1][hpos] = (double)cur.hb;
-      }
-      const ms_row nxt = r + 1 < rend ? fetch(r + 1) : ms_row{0, 0, 0, 0};
-      // one barrier per row: buffer `par` was last read two rows ago, before the barrier of
-      // the row between
-      __syncthreads();
-      if (r >= 0 && r < lv.h) {
-        double h[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int k = 0; k < 11; ++k) {
-          const double a = s_row[par][0][t + 3 * k], b = s_row[par][1][t + 3 * k];
-          const double ga = sc_g(k) * a, gb = sc_g(k) * b;
-          h[0] += ga;
-          h[1] += gb;
-          h[2] = fma(ga, a, h[2]);
-          h[3] = fma(gb, b, h[3]);
-          h[4] = fma(ga, b, h[4]);
-        }
-#pragma unroll
-        for (int j = 0; j < 5; ++j) ring[u][j] = h[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) ring[u][j] = 0.0;  // zero padding above and below
-      }
-      if (it >= 10) {  // output row r - 5: input rows r-10 .. r are slots u+1 .. u+11 (mod 11)
-        double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int k = 0; k < 11; ++k)
-#pragma unroll
-          for (int j = 0; j < 5; ++j) v[j] = fma(sc_g(k), ring[(u + 1 + k) % 11][j], v[j]);
-        const double m11 = v[0] * v[0], m22 = v[1] * v[1], m12 = v[0] * v[1];
-        const double s1 = v[2] - m11, s2 = v[3] - m22, s12 = v[4] - m12;
-        double num = 2.0 * s12 + C2, den = s1 + s2 + C2;
-        if (last) {  // l * cs as one quotient, the form of synth_score_kernel
-          num *= 2.0 * m12 + C1;
-          den *= m11 + m22 + C1;
-        }
-        if (colok) acc += num / den;
-      }
-      cur = nxt;
-      ++it;
-    }
-  }
-
-  s_red[t] = acc;
-  __syncthreads();
-#pragma unroll
-  for (int k = 128; k > 0; k >>= 1) {
-    if (t < k && t + k < MS_IT) s_red[t] += s_red[t + k];
-    __syncthreads();
-  }
+  lds_tree_sum<SW_IT>(acc, s_red);
   if (t == 0) ((double*)p.ws)[(long long)f * q.blocks + bid] = s_red[0];
 }
 
@@ -367,7 +284,7 @@ int dvie_synth_msssim(const dvie_synth_msssim_desc* d, void* stream) {
                     (unsigned)q.N);
     DVIE_LAUNCH(msssim_pyramid_kernel, grid, dim3(PY_THREADS), 0, s, *d, q);
   }
-  DVIE_LAUNCH(msssim_level_kernel, dim3((unsigned)q.blocks, (unsigned)q.N), dim3(MS_IT), 0, s, *d, q);
+  DVIE_LAUNCH(msssim_level_kernel, dim3((unsigned)q.blocks, (unsigned)q.N), dim3(SW_IT), 0, s, *d, q);
   DVIE_LAUNCH(msssim_finalize_kernel, dim3((unsigned)q.N), dim3(64 * MS_MAXK), 0, s, *d, q);
   DVIE_RETURN_LAUNCH();
 }

@@ -21,7 +21,7 @@
 // shuffles, and the pixel's cosine dot / (sqrtf(saa) * sqrtf(sbb)) (cosnhwc_kernel's expression,
 // 0/0 = NaN included) is added in float64 by the pixel's first lane.  A block of 256 threads
 // walks COS_IT passes of 256 / L pixels of ONE image (blockIdx.y), sums its 256 float64 values
-// through a fixed LDS tree and writes one partial: no atomics, the same bits every run.
+// through the fixed LDS tree of common.h and writes one partial: no atomics, the same bits every run.
 //
 // cosfeat_finalize_kernel: one block per image; per tap the partials are summed in index order
 // per thread and through the same fixed tree, divided by the tap's pixel count, and the taps'
@@ -74,19 +74,6 @@ __device__ __forceinline__ void cos_fma4(const f32x4 a, const f32x4 b, float& do
     saa += a[k] * a[k];
     sbb += b[k] * b[k];
   }
-}
-
-// the float64 values of a block's 256 threads, summed through a fixed tree; the sum in thread 0
-__device__ __forceinline__ double cos_block_sum(double v, double* s_d) {
-  const int t = threadIdx.x;
-  s_d[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int k = COS_TB / 2; k > 0; k >>= 1) {
-    if (t < k) s_d[t] += s_d[t + k];
-    __syncthreads();
-  }
-  return s_d[0];
 }
 
 }  // namespace
@@ -156,8 +143,8 @@ __global__ __launch_bounds__(COS_TB) void cosfeat_kernel(const dvie_cosfeat_desc
     }
     if (live && sub == 0) acc += (double)(dot / (sqrtf(saa) * sqrtf(sbb)));
   }
-  const double v = cos_block_sum(acc, s_d);
-  if (t == 0) p.ws[((long long)p.tap * p.n + img) * p.ws_blocks + blockIdx.x] = v;
+  lds_tree_sum<COS_TB>(acc, s_d);
+  if (t == 0) p.ws[((long long)p.tap * p.n + img) * p.ws_blocks + blockIdx.x] = s_d[0];
 }
 
 __global__ __launch_bounds__(COS_TB) void cosfeat_finalize_kernel(const dvie_cosfeat_desc p) {
@@ -168,7 +155,8 @@ __global__ __launch_bounds__(COS_TB) void cosfeat_finalize_kernel(const dvie_cos
     const double* w = p.ws + ((long long)tap * p.n + img) * p.ws_blocks;
     double s = 0.0;
     for (int j = t; j < p.blocks[tap]; j += COS_TB) s += w[j];
-    const double v = cos_block_sum(s, s_d);
+    lds_tree_sum<COS_TB>(s, s_d);
+    const double v = s_d[0];
     __syncthreads();  // (s_d[0] is read by every thread before the next tap writes it)
     total += v / (double)p.px[tap];
   }

@@ -35,6 +35,7 @@
 // otherwise it copies its piece of the nearer input slot over the interior slot: 16-byte moves when
 // both slot bases are 16-byte aligned, bytes otherwise and for the tail.
 #include "common.h"
+#include "pixel.h"
 
 namespace dvie {
 
@@ -123,10 +124,6 @@ __device__ __forceinline__ void sn_words(const sn_raw& r, const uint8_t* frame, 
   }
 }
 
-__device__ __forceinline__ uint32_t sn_luma(uint32_t px) {  // px = R | G << 8 | B << 16
-  return (77u * (px & 255u) + 150u * ((px >> 8) & 255u) + 29u * ((px >> 16) & 255u) + 128u) >> 8;
-}
-
 __device__ __forceinline__ uint32_t sn_absdiff4(uint32_t a, uint32_t b) {  // sum of |a_k - b_k| over the four bytes
   uint32_t s = 0;
 #pragma unroll
@@ -179,7 +176,7 @@ __global__ __launch_bounds__(SN_T) void synth_scene_kernel(const dvie_synth_scen
                              ((s[1] >> 16) | (s[2] << 16)) & 0xffffffu, s[2] >> 8};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const uint32_t y = sn_luma(q[k]);
+        const uint32_t y = px_luma(q[k]);
         if (4 * g + k < nx) {
           cur[g] |= y << (8 * k);
           atomicAdd(&s_hist[par][wave][y >> 3], 1u);

@@ -17,9 +17,13 @@
 // stores are whole dwords of one contiguous run per wave (3 dwords of RGB, 1 of labels per
 // quad).  More pixels per lane would widen the stores but spread each load instruction over
 // four times the address range; the NCHW pack measured slower that way (profiles/r06/nchw4).
+//
+// The per-pixel arithmetic (normalise, quantise, argmax, the quad's label store, the canvas
+// geometry) is pixel.h's, shared with tile.hip.
 #include <math.h>
 
 #include "common.h"
+#include "pixel.h"
 
 namespace dvie {
 
@@ -33,18 +37,9 @@ __global__ __launch_bounds__(256) void synth_load_kernel(const dvie_synth_load_d
   if (q == 0) {
     const uint8_t* s = p.frames + pix * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = ((float)s[c] / 255.f - 0.5f) / 0.5f;  // = clip.hip's, bit for bit
+    for (int c = 0; c < 3; ++c) v[c] = px_normalise(s[c]);
   }
   *(f32x4*)(p.out + pix * p.out_ld + 4 * q) = v;
-}
-
-// t * 127.5 + 127.5 with the multiply and the add rounded separately: an fma changes bits at the
-// half-points (43.5 comes out just below and rounds to 43).  HIP's __fmul_rn / __fadd_rn are a
-// plain * and +, which the default -ffp-contract=fast fuses, so contraction is switched off here.
-__device__ __forceinline__ float scale_unfused(float t) {
-#pragma clang fp contract(off)
-  const float m = t * 127.5f;
-  return m + 127.5f;
 }
 
 // kDword: frame and label are 4-byte aligned, so whole quads store dwords; partial quads (the
@@ -58,28 +53,9 @@ __global__ __launch_bounds__(256) void synth_finish_kernel(const dvie_synth_fini
   if (p.frame) {
     const f32x4 v = *(const f32x4*)(p.rgb + pp * p.rgb_ld);  // v[3] is padding: loaded, never used
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float t = fminf(fmaxf(v[c], -1.f), 1.f);
-      const float u = rintf(scale_unfused(t));  // half to even, in [0, 255]
-      rgb |= (uint32_t)(int)u << (8 * c);
-    }
+    for (int c = 0; c < 3; ++c) rgb |= (uint32_t)px_quantise(v[c]) << (8 * c);
   }
-  if (p.label) {
-    const float* s = p.seg + pp * p.seg_ld;
-    float best = -INFINITY;  // (an all -inf row keeps index 0, as argmax does)
-    int bi = 0;
-#pragma unroll 2
-    for (int c0 = 0; c0 < p.n_classes; c0 += 4) {
-      const f32x4 v = *(const f32x4*)(s + c0);
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (c0 + k < p.n_classes && v[k] > best) {  // padding channels never compared
-          best = v[k];
-          bi = c0 + k;
-        }
-    }
-    lab = (uint32_t)bi;
-  }
+  if (p.label) lab = (uint32_t)argmax_logits(p.seg + pp * p.seg_ld, p.n_classes);
   const int j = threadIdx.x & 3;
   const long long q0 = pix - j;  // first pixel of this lane's quad (a multiple of 4)
   const bool full = kDword && q0 + 3 < p.npix;
@@ -91,12 +67,7 @@ __global__ __launch_bounds__(256) void synth_finish_kernel(const dvie_synth_fini
       const uint32_t d = j == 0 ? (r0 | (r1 << 24)) : (j == 1 ? ((r1 >> 8) | (r2 << 16)) : ((r2 >> 16) | (r3 << 8)));
       if (full && j < 3) ((uint32_t*)(p.frame + 3 * q0))[j] = d;
     }
-    if (p.label) {
-      uint32_t w = lab << (8 * j);
-      w |= __shfl_xor(w, 1);
-      w |= __shfl_xor(w, 2);
-      if (full && j == 0) *(uint32_t*)(p.label + q0) = w;
-    }
+    if (p.label) label_quad_store(p.label + q0, lab, full);
   }
   if (!full && live) {
     if (p.frame) {
@@ -117,14 +88,14 @@ __global__ __launch_bounds__(256) void synth_load_pad_kernel(const dvie_synth_lo
   const int e = blockIdx.y * 256 + threadIdx.x;
   if (e >= p.wp * ldq) return;
   const int x = e / ldq, q = e - x * ldq;
-  const int row = blockIdx.x, img = row / p.hp, y = row - img * p.hp;
-  const long long pix = (long long)row * p.wp + x;
+  const canvas_pos cv = canvas_row(p.hp);
+  const long long pix = (long long)cv.row * p.wp + x;
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
   if (q == 0) {
-    const long long src = ((long long)img * p.h + min(y, p.h - 1)) * p.w + min(x, p.w - 1);
+    const long long src = ((long long)cv.img * p.h + min(cv.y, p.h - 1)) * p.w + min(x, p.w - 1);
     const uint8_t* s = p.frames + src * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = ((float)s[c] / 255.f - 0.5f) / 0.5f;  // = synth_load_kernel's, bit for bit
+    for (int c = 0; c < 3; ++c) v[c] = px_normalise(s[c]);
     if (p.labels) p.label_out[pix] = p.labels[src];
   }
   *(f32x4*)(p.out + pix * p.out_ld + 4 * q) = v;
@@ -139,47 +110,22 @@ template <bool kCanvasDword>
 __global__ __launch_bounds__(256) void synth_finish_crop_kernel(const dvie_synth_finish_crop_desc p) {
   const int x = blockIdx.y * 256 + threadIdx.x;
   if (x >= p.wp) return;  // (whole quads: wp and 256 are multiples of 4)
-  const int row = blockIdx.x, img = row / p.hp, y = row - img * p.hp;
-  const bool inside = y < p.h && x < p.w;
+  const canvas_pos cv = canvas_row(p.hp);
+  const bool inside = cv.y < p.h && x < p.w;
   if (!inside && !p.label_canvas) return;  // (no exchange follows without label_canvas)
-  const long long pix = (long long)row * p.wp + x;
-  uint32_t lab;
-  {  // = synth_finish_kernel's argmax, expression for expression
-    const float* s = p.seg + pix * p.seg_ld;
-    float best = -INFINITY;
-    int bi = 0;
-#pragma unroll 2
-    for (int c0 = 0; c0 < p.n_classes; c0 += 4) {
-      const f32x4 v = *(const f32x4*)(s + c0);
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (c0 + k < p.n_classes && v[k] > best) {
-          best = v[k];
-          bi = c0 + k;
-        }
-    }
-    lab = (uint32_t)bi;
-  }
+  const long long pix = (long long)cv.row * p.wp + x;
+  const uint32_t lab = (uint32_t)argmax_logits(p.seg + pix * p.seg_ld, p.n_classes);
   if (p.label_canvas) {
-    if (kCanvasDword) {
-      const int j = threadIdx.x & 3;
-      uint32_t w = lab << (8 * j);
-      w |= __shfl_xor(w, 1);
-      w |= __shfl_xor(w, 2);
-      if (j == 0) *(uint32_t*)(p.label_canvas + pix) = w;
-    } else {
+    if (kCanvasDword)
+      label_quad_store(p.label_canvas + pix, lab);
+    else
       p.label_canvas[pix] = (uint8_t)lab;
-    }
   }
   if (inside) {
-    const long long o = ((long long)img * p.h + y) * p.w + x;
+    const long long o = ((long long)cv.img * p.h + cv.y) * p.w + x;
     const f32x4 v = *(const f32x4*)(p.rgb + pix * p.rgb_ld);  // v[3] is padding: loaded, never used
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {  // = synth_finish_kernel's quantisation
-      const float t = fminf(fmaxf(v[c], -1.f), 1.f);
-      const float u = rintf(scale_unfused(t));
-      p.frame[3 * o + c] = (uint8_t)(int)u;
-    }
+    for (int c = 0; c < 3; ++c) p.frame[3 * o + c] = (uint8_t)px_quantise(v[c]);
     p.label[o] = (uint8_t)lab;
   }
 }

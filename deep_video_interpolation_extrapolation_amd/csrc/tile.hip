@@ -2,7 +2,7 @@
 // the label canvas and the kept fp32 form of the whole canvas, in one launch (include/dvie.h has the
 // blend rule, tests/tile_ref.py its numpy restatement; DESIGN.md "Tiled synthesis" the numbers).
 //
-// A gather: one lane owns one CANVAS pixel (finish_crop's geometry: blockIdx.x = image * hp + y,
+// A gather: one lane owns one CANVAS pixel (pixel.h's canvas_row: blockIdx.x = image * hp + y;
 // blockIdx.y = the 256-pixel chunk of the row) and reads the tiles that cover it, so every output
 // byte has one owner, nothing is accumulated in memory and the result cannot depend on the launch
 // geometry.  The row is uniform over a block, hence so are the tile rows that cover it (a scalar
@@ -10,11 +10,13 @@
 // (the start arrays live in the kernel arguments and are only ever read at a uniform index).
 //
 // Two paths.  Exactly one covering tile (most of the canvas): the lane copies that tile's pixel --
-// finish_crop's loads and argmax, nothing is multiplied.  Otherwise the lane walks the covering
-// tiles in ascending tile index: the image once, the logits four channels at a time (a walk per
-// channel group, so the accumulators are one f32x4 whatever n_classes is; the argmax compares the
-// blended group and moves on, no blended logit is stored anywhere).  Only waves that touch a seam
-// diverge; both paths meet again before the quad exchange of the label canvas.
+// 16-byte loads and pixel.h's argmax_logits, nothing is multiplied.  Otherwise the lane walks the
+// covering tiles in ascending tile index: the image once, the logits four channels at a time (a
+// walk per channel group, so the accumulators are one f32x4 whatever n_classes is; argmax_step
+// compares the blended group and moves on, no blended logit is stored anywhere).  Only waves that
+// touch a seam diverge; both paths meet again before the quad exchange of the label canvas.  The
+// quantisation, the argmax and the label store are pixel.h's, shared with synth.hip, so the tiled
+// path equals the untiled one where one tile covers a pixel.
 //
 // Streaming, HBM-bound, no LDS: 16-byte loads of a pixel's own 32 + 96 bytes as in finish (the
 // lanes of a wave are one pixel row apart and consume every fetched line), dword stores of the
@@ -22,15 +24,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "pixel.h"
 
 namespace dvie {
-
-// t * 127.5 + 127.5, the multiply and the add rounded separately (= synth.hip's scale_unfused)
-__device__ __forceinline__ float tile_scale_unfused(float t) {
-#pragma clang fp contract(off)
-  const float m = t * 127.5f;
-  return m + 127.5f;
-}
 
 // acc + w * v per channel, the multiply and the add rounded separately (-ffp-contract=fast would
 // fuse the plain expression into an fma)
@@ -48,12 +44,13 @@ __device__ __forceinline__ int tile_axis_w(int c, int s, int e, int S, int ov) {
 }
 
 // kDword: wp % 4 == 0 and label_canvas is 4-byte aligned, so a quad of lanes is four pixels of one
-// canvas row and stores one dword of labels (finish_crop's exchange); bytes otherwise.
+// canvas row and stores one dword of labels (label_quad_store); bytes otherwise.
 template <bool kDword>
 __global__ __launch_bounds__(256) void synth_tile_blend_kernel(const dvie_synth_tile_blend_desc p) {
   const int x = blockIdx.y * 256 + threadIdx.x;
   if (x >= p.wp) return;  // (kDword: whole quads)
-  const int row = blockIdx.x, img = row / p.hp, y = row - img * p.hp;
+  const canvas_pos cv = canvas_row(p.hp);
+  const int row = cv.row, img = cv.img, y = cv.y;
   const bool inside = y < p.h && x < p.w;
   const bool want_seg = inside || p.label_canvas != nullptr;
   const bool want_rgb = inside || p.rgb_out != nullptr;
@@ -83,22 +80,7 @@ __global__ __launch_bounds__(256) void synth_tile_blend_kernel(const dvie_synth_
     // ---- one covering tile: its values as they are ----
     const long long src = ((((long long)iy0 * p.ntx + ix0) * p.n + img) * p.th + (y - ys0)) * p.tw + (x - xs0);
     if (want_rgb) c = *(const f32x4*)(p.rgb_tiles + src * p.rgb_ld);  // c[3] is padding: loaded, never used
-    if (want_seg) {  // = synth_finish_kernel's argmax, expression for expression
-      const float* s = p.seg_tiles + src * p.seg_ld;
-      float best = -INFINITY;
-      int bi = 0;
-#pragma unroll 2
-      for (int c0 = 0; c0 < p.n_classes; c0 += 4) {
-        const f32x4 v = *(const f32x4*)(s + c0);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (c0 + k < p.n_classes && v[k] > best) {
-            best = v[k];
-            bi = c0 + k;
-          }
-      }
-      lab = (uint32_t)bi;
-    }
+    if (want_seg) lab = (uint32_t)argmax_logits(p.seg_tiles + src * p.seg_ld, p.n_classes);
   } else {
     // ---- a seam: the weighted mean over the covering tiles, ascending tile index ----
     int wsum = 0;
@@ -135,13 +117,7 @@ __global__ __launch_bounds__(256) void synth_tile_blend_kernel(const dvie_synth_
             }
           }
         }
-        const f32x4 v = a4 / fs;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (c0 + k < p.n_classes && v[k] > best) {  // padding channels never compared
-            best = v[k];
-            bi = c0 + k;
-          }
+        argmax_step(a4 / fs, c0, p.n_classes, best, bi);
       }
       lab = (uint32_t)bi;
     }
@@ -153,24 +129,15 @@ __global__ __launch_bounds__(256) void synth_tile_blend_kernel(const dvie_synth_
     for (int k = 4; k < p.rgb_ld; k += 4) *(f32x4*)(o + k) = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if (p.label_canvas) {
-    if (kDword) {
-      const int j = threadIdx.x & 3;
-      uint32_t w = lab << (8 * j);
-      w |= __shfl_xor(w, 1);
-      w |= __shfl_xor(w, 2);
-      if (j == 0) *(uint32_t*)(p.label_canvas + pix) = w;
-    } else {
+    if (kDword)
+      label_quad_store(p.label_canvas + pix, lab);
+    else
       p.label_canvas[pix] = (uint8_t)lab;
-    }
   }
   if (inside) {
     const long long o = ((long long)img * p.h + y) * p.w + x;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {  // = synth_finish_kernel's quantisation
-      const float t = fminf(fmaxf(c[k], -1.f), 1.f);
-      const float u = rintf(tile_scale_unfused(t));
-      p.frame[3 * o + k] = (uint8_t)(int)u;
-    }
+    for (int k = 0; k < 3; ++k) p.frame[3 * o + k] = (uint8_t)px_quantise(c[k]);
     p.label[o] = (uint8_t)lab;
   }
 }
